@@ -7,6 +7,7 @@ the adaptive bound never stops early).  Every rank runs its own pairs (weak scal
 the only collective is the final gather of per-rank counters.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cal|sf|tf|scannet]
+                    [--dump-outputs DIR] [--full]
 
 --workload scannet runs configs[4] instead: a fixed set of 1500 shared-focal pairs
 split over the ranks, many pairs in flight per GPU; value = pairs/s, plus pose
@@ -14,9 +15,14 @@ AUC@5/10/20 over all pairs.
 
 Prints ONE JSON line on rank 0.  `value` = hypotheses scored per second by the whole
 job; `roofline` prices the score_batch kernel at the algorithmic 48*N bytes per
-hypothesis against its HIP-event device time; `cpu_baseline` times the CPU oracle
-(test infrastructure, a scalar restatement of the reference) on a bounded sample of
-the same pair.
+hypothesis against its HIP-event device time.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --dump-outputs
+DIR also writes what the last timed step returned (rank 0's) as DIR/<name>.npy.  --full
+adds the untimed legs after the timed steps: `cpu_baseline` times the CPU oracle (test
+infrastructure, a scalar restatement of the reference) on a bounded sample of the same
+pair, `pairs_in_flight` times the pairs again several at a time, and the ScanNet
+stand-in reruns its pairs in the reference's point-only mode (`point_only_baseline`).
 """
 import argparse
 import json
@@ -476,6 +482,46 @@ def records_of(eng, seeds, res, pairs):
     return [result_record(s, m, st, p, (et[k], eR[k])) for k, (s, (m, st), p) in enumerate(zip(seeds, res, pairs))]
 
 
+DUMP_MASK_PAIRS = 64  # pairs of a step whose inlier masks are dumped (the step's first ones)
+
+
+def dump_outputs(path, seeds, res, pairs):
+    """--dump-outputs: what the timed path returned to its caller in its last step (one
+    pair for configs[1..3], every pair of this rank for the ScanNet stand-in), as
+    path/<name>.npy in float64, one row per pair: the model (pose, scale_offsets, and
+    focals where the model has them), the statistics a caller reads (stats, columns
+    DUMP_STATS; the timings are left out) and the inlier index lists of the step's first
+    DUMP_MASK_PAIRS pairs as 0/1 masks over the correspondences (inlier_masks, zero-padded
+    to the longest pair).  The pairs are seeded, so two builds run with the same
+    arguments dump outputs of the same inputs."""
+    os.makedirs(path, exist_ok=True)
+    n = len(res)
+    pose = np.stack([np.asarray(m.pose, dtype=np.float64).reshape(3, 4) for m, _ in res])
+    so = np.array([[m.scale, m.offset0, m.offset1] for m, _ in res], dtype=np.float64)
+    stats = np.array([[st.num_iterations_total] + list(st.num_iterations_per_solver) +
+                      [st.best_num_inliers, st.best_solver_type, st.best_model_score] + list(st.inlier_ratios) +
+                      [len(ix) for ix in st.inlier_indices] + [st.number_lo_iterations] for _, st in res],
+                     dtype=np.float64).reshape(n, len(DUMP_STATS))
+    k = min(n, DUMP_MASK_PAIRS)
+    width = max(len(p["x0"]) for p in pairs[:k])
+    masks = np.zeros((k, 3, width), dtype=np.float64)
+    for j, (_, st) in enumerate(res[:k]):
+        for t, ix in enumerate(st.inlier_indices):
+            masks[j, t, np.asarray(ix, dtype=np.int64)] = 1.0
+    out = {"seeds": np.asarray(seeds, dtype=np.float64), "pose": pose, "scale_offsets": so, "stats": stats,
+           "inlier_masks": masks}
+    if hasattr(res[0][0], "focal") or hasattr(res[0][0], "focal0"):  # (the calibrated model has no focal)
+        out["focals"] = np.array([[getattr(m, k, getattr(m, "focal", None)) for k in ("focal0", "focal1")]
+                                  for m, _ in res], dtype=np.float64)
+    for name, arr in out.items():
+        np.save(os.path.join(path, name + ".npy"), arr)
+
+
+DUMP_STATS = ["num_iterations_total", "num_iterations_solver0", "num_iterations_solver1", "best_num_inliers",
+              "best_solver_type", "best_model_score", "inlier_ratio0", "inlier_ratio1", "inlier_ratio2", "num_inliers0",
+              "num_inliers1", "num_inliers2", "number_lo_iterations"]
+
+
 def shard_scannet(total, world, rank):
     """configs[4] pairs of this rank: longest-processing-time-first over the pair sizes
     (work ~ N x iterations); deterministic, every rank computes the same
@@ -508,6 +554,8 @@ def run_scannet(a, wl, world, rank, dev, barrier, eng):
         res = eng.estimate_batch(wl["variant"], pairs, o, c, device=dev, num_streams=a.streams)
     barrier()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, seeds, res, pairs)
     recs = records_of(eng, seeds, res, pairs)
     local = [elapsed, float(len(pairs) * a.steps), float(sum(st.num_hypotheses for _, st in res) * a.steps),
              float(sum(st.num_iterations_total for _, st in res) * a.steps)]
@@ -783,12 +831,21 @@ def main(argv=None):
                     help="configs[1..3]: also time the pairs k at a time on the GPU (secondary figure; 1 = skip)")
     ap.add_argument("--no-point-only", dest="point_only", action="store_false",
                     help="scannet: skip the untimed point-only baseline pass")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the untimed legs after the timed steps: the CPU baselines (--cpu-budget), the "
+                         "pairs-in-flight figure (--in-flight), scannet's point-only baseline pass")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to its caller as DIR/<name>.npy (float64)")
     ap.add_argument("--engine-module", default=None, help=argparse.SUPPRESS)
     a = ap.parse_args(argv)
+    if not a.full:  # a plain run: set up, warm up, the timed steps, the result line
+        a.cpu_budget, a.in_flight, a.point_only = 0.0, 1, False
     if a.steps is None:
         a.steps = 10 if a.workload == "scannet" else 40
     if a.warmup is None:
         a.warmup = 2 if a.workload == "scannet" else 4
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     wl = WORKLOADS[a.workload]
 
     if "WORLD_SIZE" not in os.environ and a.gpus is not None and a.gpus > 1:
@@ -886,6 +943,8 @@ def main(argv=None):
     eng.profile_enable(False)
     prof = eng.profile_read()
 
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, seeds[-1:], res[-1:], pairs[-1:])
     recs = records_of(eng, seeds[a.warmup:a.warmup + len(res)], res, pairs[a.warmup:a.warmup + len(res)])
     local = [elapsed, hyps, iters, lo, t_lo, prof["score_ms"], prof["solve_ms"], prof["hypotheses"],
              prof["correspondences"], prof["batches"], prof["sweeps"], prof["lm_calls"], prof["lm_wall_ms"],

@@ -163,7 +163,7 @@ def test_cpu_partition_follows_gpu_locality():
 
 def test_gpus_flag_scannet_shards_all_pairs():
     res = _run_bench(["--gpus", "2", "--workload", "scannet", "--pairs", "9", "--steps", "1", "--warmup", "0",
-                      "--cpu-budget", "0", "--engine-module", "tests.bench_stub_engine"])
+                      "--full", "--cpu-budget", "0", "--engine-module", "tests.bench_stub_engine"])
     assert res["n_gpus"] == 2 and res["config"]["pairs"] == 9
     assert res["results"]["records"] == 9 and res["results"]["pairs_disjoint"]
     assert res["pose_auc"]["pairs"] == 9
@@ -207,14 +207,63 @@ def test_records_summary_and_gather_single_rank():
 def test_single_rank_in_flight_leg_and_records():
     """One rank: the pairs-in-flight secondary figure (estimate_batch k at a time) sits
     beside `value` without replacing it, and the records carry the engine's pose errors."""
-    res = _run_bench(["--steps", "4", "--warmup", "1", "--cpu-budget", "0", "--in-flight", "3", "--engine-module",
-                      "tests.bench_stub_engine"])
+    res = _run_bench(["--steps", "4", "--warmup", "1", "--full", "--cpu-budget", "0", "--in-flight", "3",
+                      "--engine-module", "tests.bench_stub_engine"])
     assert res["n_gpus"] == 1 and res["value"] > 0
     pf = res["pairs_in_flight"]
     assert pf["pairs"] == 4 and pf["in_flight"] == 3 and pf["hypotheses_per_s"] > 0
     assert res["results"]["records"] == 4
     # the stub returns R = I, t = (1, 0, 0): its pose errors come from compute_pose_error
     assert res["results"]["median_pose_err_deg"] >= 0.0
+
+
+def test_plain_run_skips_the_untimed_legs_and_dumps_its_last_step(tmp_path):
+    """Without --full the legs after the timed steps do not run, whatever their own
+    options say; --dump-outputs writes the last timed step's model and statistics
+    (one pair: seed warmup + steps - 1 of rank 0) as float64 arrays."""
+    d = tmp_path / "out"
+    res = _run_bench(["--gpus", "1", "--steps", "3", "--warmup", "2", "--in-flight", "3", "--dump-outputs", str(d),
+                      "--engine-module", "tests.bench_stub_engine"])
+    assert "pairs_in_flight" not in res and res["cpu_baseline"] is None
+    assert res["steps"] == 3 and res["results"]["records"] == 3 and res["ms_per_step"] > 0
+    got = {p.name: np.load(p) for p in d.iterdir()}
+    # (the calibrated model has no focal length: no focals.npy)
+    assert sorted(got) == ["inlier_masks.npy", "pose.npy", "scale_offsets.npy", "seeds.npy", "stats.npy"]
+    assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in got.values())
+    assert got["seeds.npy"].tolist() == [4.0]
+    assert np.array_equal(got["pose.npy"], np.hstack([np.eye(3), [[1.0], [0.0], [0.0]]])[None])
+    assert got["scale_offsets.npy"].tolist() == [[1.0, 0.0, 0.0]]
+    sys.path.insert(0, ROOT)
+    import bench
+
+    st = dict(zip(bench.DUMP_STATS, got["stats.npy"][0]))
+    assert st["num_iterations_total"] == 100000 and st["best_num_inliers"] == 2000 and st["best_model_score"] == 2000.0
+    assert got["inlier_masks.npy"].shape == (1, 3, 2000)
+
+
+def test_dump_outputs_of_a_many_pair_step(tmp_path):
+    """The ScanNet stand-in's step returns one result per pair: one row each, the inlier
+    lists of the first DUMP_MASK_PAIRS pairs as masks padded to the longest of them."""
+    sys.path.insert(0, ROOT)
+    import bench
+    from madpose_amd.api import HybridRansacStatistics, PoseScaleOffsetSharedFocal
+
+    n = bench.DUMP_MASK_PAIRS + 3
+    pairs = [{"x0": np.zeros((5 + k % 4, 2))} for k in range(n)]
+    res = []
+    for k in range(n):
+        st = HybridRansacStatistics()
+        st.inlier_indices = [[0, k % 5], [], [4]]
+        res.append((PoseScaleOffsetSharedFocal(np.eye(3), np.array([0.0, 1.0, 0.0]), 2.0, 0.25, 0.5, 500.0 + k), st))
+    bench.dump_outputs(str(tmp_path), list(range(n)), res, pairs)
+    assert np.load(tmp_path / "pose.npy").shape == (n, 3, 4)
+    assert np.load(tmp_path / "focals.npy")[3].tolist() == [503.0, 503.0]
+    assert np.load(tmp_path / "scale_offsets.npy")[-1].tolist() == [2.0, 0.25, 0.5]
+    stats = np.load(tmp_path / "stats.npy")
+    assert stats.shape == (n, len(bench.DUMP_STATS)) and stats[7, bench.DUMP_STATS.index("num_inliers0")] == 2
+    masks = np.load(tmp_path / "inlier_masks.npy")
+    assert masks.shape == (bench.DUMP_MASK_PAIRS, 3, 8)
+    assert masks[7].tolist() == [[1, 0, 1, 0, 0, 0, 0, 0], [0] * 8, [0, 0, 0, 0, 1, 0, 0, 0]]
 
 
 def test_forced_one_rank_group_gathers_through_the_collective():

@@ -7,7 +7,7 @@ mkdir -p "$out"
 for rep in $(seq 1 "$reps"); do
   for tree in new old; do
     d=.; [ $tree = old ] && d=ab_old
-    (cd $d && timeout -k 10 200 python bench.py --cpu-budget 0 --steps 40) > "$out/cal_${tree}_$rep.json" 2>/dev/null || exit $?
+    (cd $d && timeout -k 10 200 python bench.py --full --cpu-budget 0 --steps 40) > "$out/cal_${tree}_$rep.json" 2>/dev/null || exit $?
     python -c 'import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); f=d["pairs_in_flight"]; print(sys.argv[2], round(d["value"]), round(d["ms_per_step"],3), "in flight", round(f["hypotheses_per_s"]), round(f["ms_per_pair"],3))' "$out/cal_${tree}_$rep.json" "cal $tree" || exit 1
   done
 done

@@ -16,10 +16,10 @@ step() { # seconds log command...
 }
 step 700 pytest_gpu.log python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread -p no:cacheprovider
 step 200 smoke.log python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')"
-step 240 bench_cal.log python -u bench.py
-step 200 bench_sf.log python -u bench.py --workload sf --cpu-budget 0
-step 200 bench_tf.log python -u bench.py --workload tf --cpu-budget 0
-step 200 bench_scannet.log python -u bench.py --workload scannet --cpu-budget 0
+step 240 bench_cal.log python -u bench.py --full
+step 200 bench_sf.log python -u bench.py --full --workload sf --cpu-budget 0
+step 200 bench_tf.log python -u bench.py --full --workload tf --cpu-budget 0
+step 200 bench_scannet.log python -u bench.py --full --workload scannet --cpu-budget 0
 step 240 prof_cal.log rocprofv3 --kernel-trace --stats -d "$out/prof_cal" -o cal -- python3 bench.py --cpu-budget 0 --in-flight 1
 step 60 cal_summary.log python tools/prof_summary.py "$out/prof_cal" "$out/cal_kernel_stats.csv"
 step 240 prof_sf.log rocprofv3 --kernel-trace --stats -d "$out/prof_sf" -o sf -- python3 bench.py --workload sf --cpu-budget 0 --in-flight 1
