@@ -102,13 +102,12 @@ class Sampler {
     // once the batch is drawn (the post-LO speculation launches it on the GPU there)
     // chain (nullable): a second batch for the same job -- once *g is drawn (and `after`
     // ran), chain->B more iterations are drawn from where it ended into chain->g (the
-    // post-LO speculation's successor, drawn while the LO runs)
+    // post-LO speculation's successor, drawn while the LO runs; only drawn: host work)
     struct Chain {
         Batch *g;
         uint32_t B;
         int slot;
         int *smp;
-        std::function<void()> after; // runs once it is drawn (launches it; nullable)
     };
     void start(const IterationStream &from, Batch *g, uint32_t B, int slot, int *smp,
                std::function<void()> after = nullptr, const Chain *chain = nullptr) {
@@ -121,7 +120,6 @@ class Sampler {
         B2_ = chain ? chain->B : 0;
         slot2_ = chain ? chain->slot : 0;
         smp2_ = chain ? chain->smp : nullptr;
-        after2_ = chain ? chain->after : nullptr;
         ok2_ = false;
         after_ = std::move(after);
         err_ = nullptr;
@@ -141,7 +139,6 @@ class Sampler {
     bool chained(IterationStream *rs) {
         std::unique_lock<std::mutex> lk(mu_);
         done_cv_.wait(lk, [this] { return !busy_; });
-        if (err2_) std::rethrow_exception(err2_);
         if (ok2_) *rs = rs2_;
         return ok2_;
     }
@@ -186,27 +183,16 @@ class Sampler {
             ok_ = ok;
             busy1_ = false; // finish() returns here: the chained batch is drawn after it
             ok2_ = false;
-            err2_ = nullptr;
             const bool go2 = ok && !err && g2;
             if (!go2) busy_ = false;
             done_cv_.notify_all();
             if (!go2) continue;
             lk.unlock();
-            std::exception_ptr err2;
             IterationStream r2 = rs_;
-            bool ok2 = draw_batch(r2, *g2, B2_, slot2_, smp2_, &abort_, sampler_mode());
-            if (ok2 && after2_) {
-                try {
-                    after2_();
-                } catch (...) {
-                    err2 = std::current_exception();
-                    ok2 = false;
-                }
-            }
+            const bool ok2 = draw_batch(r2, *g2, B2_, slot2_, smp2_, &abort_, sampler_mode());
             lk.lock();
             rs2_ = r2;
             ok2_ = ok2;
-            err2_ = err2;
             busy_ = false;
             done_cv_.notify_all();
         }
@@ -220,13 +206,12 @@ class Sampler {
     int *smp_ = nullptr;
     std::function<void()> after_;
     Batch *g2_ = nullptr;
-    std::function<void()> after2_;
     uint32_t B2_ = 0;
     int slot2_ = 0;
     int *smp2_ = nullptr;
     IterationStream rs1_, rs2_; // the streams after the batch / after the chained one
     bool ok2_ = false;
-    std::exception_ptr err_, err2_;
+    std::exception_ptr err_;
     std::atomic<bool> abort_{false};
     bool busy_ = false, busy1_ = false, ok_ = false, quit_ = false; // busy1_: the first batch is drawing
     uint64_t gen_ = 0;
@@ -387,8 +372,9 @@ inline int lo_lanes_setting() {
 // Device context: stream + cached buffers (one per device and concurrent caller)
 //
 // The per-batch buffers come in two slots (BatchBufs), the slot of a batch being the
-// host sample slot it was drawn into: the continuation batch is launched into the other
-// slot while the host still reads this one's results (early continuation, Run::run).
+// host sample slot it was drawn into: the next batch is drawn into the other slot while
+// this one is on the GPU, and the post-LO speculation is launched from there while the
+// host still works on this one's results (Run::run).
 struct BatchBufs {
     int *d_counts = nullptr;
     IterResult *d_res = nullptr;
@@ -410,10 +396,9 @@ struct BatchBufs {
     hipEvent_t ev_h2d = nullptr;                    // the batch's samples have been copied
     hipEvent_t ev_solved = nullptr;                 // the batch's solver kernels are done
     hipEvent_t ev_done = nullptr;                   // the batch's results are on the host
-    // each slot's batches run on the slot's stream from the slot's sample buffer: a
-    // continuation in the other slot solves while this slot's batch is scored (it waits
-    // for this slot's ev_solved first: the point solvers' workspace and the MD side
-    // stream are shared)
+    // each slot's batches run on the slot's stream from the slot's sample buffer; a
+    // batch waits for the other slot's ev_solved before it solves (the point solvers'
+    // workspace and the MD side stream are shared)
     hipStream_t stream = nullptr;
     int *d_samples = nullptr;
     unsigned epoch_hi = 0;                          // ~epoch of the batch last launched here
@@ -497,7 +482,7 @@ struct DeviceCtx {
         const int64_t nn = std::max<int64_t>(std::max<int64_t>(n, cap_n), 64);
         const int bb_ = std::max(B, cap_b), mm = std::max(M, cap_m);
         MP_HIP(hipSetDevice(device));
-        MP_HIP(hipDeviceSynchronize()); // (an early continuation may still use the old buffers)
+        MP_HIP(hipDeviceSynchronize()); // (a batch of an unwound run may still use the old buffers)
         free_all();
         MP_HIP(hipMalloc(&d_pair, sizeof(double) * 12 * nn));
         MP_HIP(hipMalloc(&d_err, sizeof(double) * 3 * nn));
@@ -615,8 +600,8 @@ std::atomic<bool> g_prof_on{false};
 std::mutex g_prof_mu;
 KernelProfile g_prof;
 
-// estimators running on each device (leases held): the early continuation is
-// speculative GPU work that pays only while one estimator has the device to itself
+// estimators running on each device (leases held): the LO workers spin for their jobs
+// only while one estimator has the device to itself (LoWorkers::spin_until)
 constexpr int kMaxDevices = 64;
 std::atomic<int> g_active_runs[kMaxDevices];
 int active_runs(int device) {
@@ -1432,7 +1417,7 @@ class Run {
                 // the speculation hook runs as job 1, beside the steps: step 0 (the
                 // longest, on all base inliers) starts at once, and the lane that takes
                 // the hook takes a short step after it (the hook may wait for the
-                // sampler thread to finish launching a continuation it cancels)
+                // sampler thread to give up the draw it cancels)
                 Mt19937 end = base_sel;
                 const bool hook_job = predicted && !hooked && X_.lo_workers->lanes() > 1;
                 if (predicted && !hooked) {
@@ -1545,31 +1530,6 @@ class Run {
     // best: best_min_model_score when the batch starts (the scoring's early exit).
     bool batch_prof_[2] = {false, false};
     double launch_s_ = 0.0; // main-thread time in launch_batch (MADPOSE_LO_TIMING)
-    // early continuation: off by default (MADPOSE_EARLY_CONT=1: on while this estimator
-    // is alone on its device, =2: always).  With 8 shared-focal pairs in flight the
-    // discarded continuations took GPU time from the other pairs (ScanNet stand-in 747
-    // -> 1064 pairs/s without them, profiles/r04/scab/); alone, an LO that cancels the
-    // continuation waits for the sampler thread to finish launching it (the speculation
-    // hook 31-48 us instead of 4 us, the LO steps phase 221-233 vs 180-194 us, cal 5.90-
-    // 5.99 vs 5.80-5.86 ms, profiles/r04/hook2/)
-    // =3: continuations of at least kEarlyMinBatch iterations while alone on the device
-    // (the growth phase, where new bests are rare): each slot has its own stream, so the
-    // continuation's solvers run while this batch is scored.  Its gating is best-effort
-    // (ADVICE r05): the continuation waits only for the previous batch's solve, so both
-    // score kernels can run at once against the one record word, and the newer epoch's
-    // atomicMin can replace the older batch's record -- the older batch's workgroups then
-    // stop skipping and the continuation is no longer cancelled by it.  Results do not
-    // change (the host walks and discards as always); a discarded continuation merely
-    // costs its full GPU time.  (On one stream, round 5's
-    // first form, it measured slower: cal 5.62 -> 5.86 ms per pair, profiles/r05/r5o.)
-    const int early_mode_ = [] {
-        return (int)env_int("MADPOSE_EARLY_CONT", 0, 0, 3);
-    }();
-    static constexpr uint32_t kEarlyMinBatch = 4096;
-    bool early_now(uint32_t Bn) const {
-        return early_mode_ == 2 || (early_mode_ == 1 && active_runs(X_.device) <= 1) ||
-               (early_mode_ == 3 && Bn >= kEarlyMinBatch && active_runs(X_.device) <= 1);
-    }
     int launch_n_ = 0;
     // big LM solves (>= kBigLM blocks) under MADPOSE_LO_TIMING: count, evaluations,
     // seconds, blocks
@@ -1589,10 +1549,18 @@ class Run {
 
     // cut_on_record: the batch lies at or past lo_starting_iterations, so its first new
     // best runs LO and cuts it; score_batch then skips the iterations behind a record.
-    // gate_prev: the batch is launched before the previous one's results were read (an
-    // early continuation); its kernels leave at once if that batch published a record
-    // (kernels.h batch_cancelled), i.e. if the host is bound to discard this one.
-    void launch_batch(const Batch &g, double best, bool cut_on_record, const BatchBufs *gate_prev = nullptr) {
+    //
+    // Threading: one thread at a time calls this for a run.  The estimator thread
+    // launches every batch but one kind, the post-LO speculation, which the sampler
+    // thread launches (the `after` of its job, Run::run speculation_hook) between
+    // Sampler::start() and the matching finish() / cancel().  The estimator thread spends
+    // that span inside local_opt, which launches no batch (its hook only starts the job),
+    // and on the few lines from there to the join (join_speculation), and it returns from
+    // finish() / cancel() only once `after` has returned.  The
+    // sampler's mutex orders the two threads at both ends, so X_.epoch, batch_prof_ and
+    // the BatchBufs fields written here (epoch_hi, h2d_pending, the events) need no
+    // atomics.  (tl_ takes its own lock: the LO's marks come from the other thread.)
+    void launch_batch(const Batch &g, double best, bool cut_on_record) {
         const uint32_t B = g.B;
         const int nmd = g.nmd, npt = g.npt;
         BatchBufs &Q = X_.bb[g.slot];
@@ -1600,11 +1568,7 @@ class Run {
         hipStream_t s = Q.stream;
         const bool prof = g_prof_on.load(std::memory_order_relaxed);
         batch_prof_[g.slot] = prof;
-        PairData D = D_;
-        if (gate_prev) {
-            D.gate = X_.d_recword;
-            D.gate_hi = gate_prev->epoch_hi;
-        }
+        const PairData &D = D_;
         // one upload: samples, then the MD list and the (descending) point list
         MP_HIP(hipMemcpyAsync(Q.d_samples, slot_for(g.slot, B), sizeof(int) * 9 * (size_t)B, hipMemcpyHostToDevice, s));
         tl_.mark("  h2d");
@@ -1656,7 +1620,8 @@ class Run {
         MP_HIP(hipStreamSynchronize(X_.md_stream));
     }
     // before host sample slot `slot` is redrawn: the last batch launched from it must
-    // have been copied to the device (an early continuation may still be queued)
+    // have been copied to the device (a run that an exception unwound leaves its batches
+    // queued; otherwise the batch has been waited for or drained by then)
     void slot_free(int slot) {
         BatchBufs &Q = X_.bb[slot];
         if (Q.h2d_pending) {
@@ -1839,97 +1804,90 @@ void Run::run(Model *best, Stats *S) {
     // of chain_B iterations from chain_at on
     bool chain_ready = false;
     uint32_t chain_at = 0, chain_B = 0;
-    // MADPOSE_LO_CHAIN_LAUNCH=1: the job also launches the chained batch, behind the
-    // speculative batch (the GPU otherwise idles for the rest of the LO), bound by the
-    // pre-LO best and gated on the speculative batch's record word (kernels.h
-    // batch_cancelled) like an early continuation; when the host discards it, the next
-    // batch in its slot follows it on the slot's stream.  Off by default: cal 4.28 ->
-    // 4.24 ms, sf 9.72 -> 9.93 ms (its discarded batches overlap the next scoring,
-    // profiles/r05/chain_launch).
-    const bool chain_launch = [] {
-        return env_flag("MADPOSE_LO_CHAIN_LAUNCH", false);
-    }();
-    auto make_chain = [&](uint32_t at, uint32_t Bs, int slot, double bound, Sampler::Chain *ch, uint32_t *ch_at,
-                          uint32_t *ch_B) {
-        const uint32_t at2 = at + Bs;
-        if (!chain_on || early_mode_ != 0 || at2 >= max_total || at2 == lo_start) return false;
-        const uint32_t B2 = batch_size(at2, grow(at2));
-        if (B2 == 0) return false;
-        slot_free(slot ^ 1);
-        Batch *g2 = &gen[slot ^ 1];
-        std::function<void()> after;
-        if (chain_launch && active_runs(X_.device) <= 1) {
-            const BatchBufs *prev = &X_.bb[slot];
-            const bool cut = at2 >= lo_start;
-            after = [this, g2, bound, cut, prev] {
-                MP_HIP(hipSetDevice(X_.device));
-                launch_batch(*g2, bound, cut, prev);
-            };
-        }
-        *ch = Sampler::Chain{g2, B2, slot ^ 1, slot_for(slot ^ 1, B2), std::move(after)};
-        *ch_at = at2;
-        *ch_B = B2;
-        return true;
+    // One post-LO speculation: what the hook started, read once local_opt has returned
+    struct Speculation {
+        bool on = false;    // the sampler holds (and launches) the post-LO batch
+        uint64_t draws = 0; // ... for an LO that leaves the selection stream at this draw count
+        bool chain = false; // ... and then draws the batch after it: chain_B iterations from chain_at
+        uint32_t chain_at = 0, chain_B = 0;
     };
-    bool chain_launched = false; // (the chained batch is on the GPU already)
+    // The hook that local_opt calls with the predicted end of the selection stream, for
+    // an LO after which iteration `at` comes next.  It runs on the estimator thread or on
+    // an LO worker beside the steps, always inside local_opt, so it gets
+    // copies of the loop state it reads -- the streams as rewound (the LO draws only from
+    // its own copies of the selection stream and writes rs_ after LoWorkers::run has
+    // returned), the free slot, the pre-LO best (LO leaves best_min_model_score alone,
+    // src/hybrid_ransac.h:149-155) -- and writes only *sp.  sampler_busy: the sampler is
+    // drawing the batch that would have come next without the LO.
+    auto speculation_hook = [&](uint32_t at, bool sampler_busy, Speculation *sp) {
+        const IterationStream rs_at_lo = rs_;
+        const int slot = cur ^ 1;
+        const double bound = best_min_score;
+        Batch *const gs = &gen[slot];
+        return [this, rs_at_lo, slot, bound, gs, at, sampler_busy, sp, max_total, speculate, chain_on, lo_start, &gen,
+                &grow, &batch_size](const Mt19937 &sel_end) {
+            if (!speculate || at >= max_total) return;
+            if (sampler_busy) X_.sampler->cancel();
+            IterationStream from = rs_at_lo;
+            from.sel = sel_end;
+            slot_free(slot);
+            const uint32_t Bs = batch_size(at, sync_batch(grow(at)));
+            // the chained batch goes into the other slot: its batch, the one that led to
+            // the LO, is spent
+            Sampler::Chain ch;
+            const uint32_t at2 = at + Bs;
+            const uint32_t B2 = chain_on && at2 < max_total && at2 != lo_start ? batch_size(at2, grow(at2)) : 0;
+            if (B2 > 0) {
+                slot_free(slot ^ 1);
+                ch = Sampler::Chain{&gen[slot ^ 1], B2, slot ^ 1, slot_for(slot ^ 1, B2)};
+            }
+            sp->chain = B2 > 0;
+            sp->chain_at = at2;
+            sp->chain_B = B2;
+            X_.sampler->start(from, gs, Bs, slot, slot_for(slot, Bs),
+                              [this, gs, bound, at, lo_start] {
+                                  // the sampler thread is not bound to the estimator's
+                                  // device by itself
+                                  MP_HIP(hipSetDevice(X_.device));
+                                  launch_batch(*gs, bound, at >= lo_start);
+                              },
+                              sp->chain ? &ch : nullptr);
+            sp->on = true;
+            sp->draws = sel_end.draws();
+        };
+    };
+    // after that LO: the speculative batch comes next if the LO ended where predicted
+    // (and the run goes on: `keep`); else it is discarded
+    auto join_speculation = [&](const Speculation &sp, bool keep) {
+        have_next = false;
+        if (keep && rs_.sel.draws() == sp.draws) {
+            tl_.mark("join_spec");
+            have_next = X_.sampler->finish(&rs_);
+            tl_.mark("joined", have_next ? 1 : 0);
+            if (have_next) {
+                cur ^= 1;
+                launched = true;
+                chain_ready = sp.chain; // (still drawing, maybe: chained() below)
+                chain_at = sp.chain_at;
+                chain_B = sp.chain_B;
+            }
+        } else {
+            X_.sampler->cancel();
+            drain_batches(); // a launched speculation drains
+        }
+    };
     while (it < max_total && !done) {
         if (it == lo_start && best_min_score < kMax) {
             ++S->number_lo_iterations;
-            // post-LO speculation as after the LOs of the walk below: the batch from
-            // lo_starting_iterations on is drawn from the predicted end of the selection
-            // stream and launched while the LO steps run (no continuation is pending:
+            // post-LO speculation as after the LOs of the walk below (the sampler is idle:
             // batches stop at lo_start)
-            bool spec0 = false;
-            uint64_t spec0_draws = 0;
-            const IterationStream rs_at_lo = rs_;
-            const int slot = cur ^ 1;
-            const double bound = best_min_score;
-            Batch *const gs = &gen[slot];
-            const uint32_t at = it;
-            bool spec0_chain = false, spec0_chain_launched = false;
-            uint32_t spec0_chain_at = 0, spec0_chain_B = 0;
-            auto predicted = [this, rs_at_lo, slot, bound, gs, at, max_total, speculate, lo_start, &grow, &batch_size,
-                              &spec0, &spec0_draws, &make_chain, &spec0_chain, &spec0_chain_at, &spec0_chain_B,
-                              &spec0_chain_launched](const Mt19937 &sel_end) {
-                if (!speculate || at >= max_total) return;
-                IterationStream from = rs_at_lo;
-                from.sel = sel_end;
-                slot_free(slot);
-                const uint32_t Bs = batch_size(at, sync_batch(grow(at)));
-                Sampler::Chain ch;
-                spec0_chain = make_chain(at, Bs, slot, bound, &ch, &spec0_chain_at, &spec0_chain_B);
-                spec0_chain_launched = spec0_chain && ch.after != nullptr;
-                X_.sampler->start(from, gs, Bs, slot, slot_for(slot, Bs),
-                                  [this, gs, bound, at, lo_start] {
-                                      MP_HIP(hipSetDevice(X_.device));
-                                      launch_batch(*gs, bound, at >= lo_start);
-                                  },
-                                  spec0_chain ? &ch : nullptr);
-                spec0 = true;
-                spec0_draws = sel_end.draws();
-            };
+            Speculation sp;
             tl_.mark("lo", (long)it);
-            local_opt(S->best_solver_type, best, &S->best_model_score, &S->best_solver_type, predicted);
-            tl_.mark("lo_end", spec0 ? 1 : 0);
+            local_opt(S->best_solver_type, best, &S->best_model_score, &S->best_solver_type,
+                      speculation_hook(it, false, &sp));
+            tl_.mark("lo_end", sp.on ? 1 : 0);
             termination(*best, max_per);
-            if (spec0) {
-                if (rs_.sel.draws() == spec0_draws) {
-                    tl_.mark("join_spec");
-                    have_next = X_.sampler->finish(&rs_);
-                    if (have_next) {
-                        cur ^= 1;
-                        launched = true;
-                        // (the chained batch may still be drawing: chained() below)
-                        chain_ready = spec0_chain;
-                        chain_at = spec0_chain_at;
-                        chain_B = spec0_chain_B;
-                        chain_launched = spec0_chain && spec0_chain_launched;
-                    }
-                } else {
-                    X_.sampler->cancel();
-                    drain_batches(); // a launched speculation drains
-                }
-            }
+            if (sp.on) join_speculation(sp, true);
         }
         // (drawn here only at the start and after LO / a cut batch: kept short so the
         // GPU starts early and the worker draws the big ones)
@@ -1959,14 +1917,7 @@ void Run::run(Model *best, Stats *S) {
         // While the batch is in flight, the sampler thread draws the next one into the
         // other slot.  It is kept if this batch neither triggers LO nor terminates (both
         // rewind the streams); never across lo_start, where an LO runs before the next
-        // batch.  Early continuation: the sampler launches it as soon as it is drawn,
-        // behind this batch on the stream, instead of after the host has read this one
-        // -- the GPU goes straight on.  A batch at or past lo_start that holds a new best
-        // runs LO and discards the continuation, and a new best that the device could
-        // prove (a published record) makes the continuation's kernels leave at once
-        // (the gate), so a discarded continuation costs almost nothing; its bound is this
-        // batch's pre-batch best, which is its own unless this batch holds a new best,
-        // and then (before lo_start) the bound is conservative and no record skip runs.
+        // batch.
         const uint32_t it_next = it + B;
         const uint32_t Bn0 = (it_next < max_total && it_next != lo_start)
                                  ? batch_size(it_next, grow(it_next))
@@ -1976,21 +1927,9 @@ void Run::run(Model *best, Stats *S) {
         if (chain_ready && !use_chain) X_.sampler->cancel(); // (not the next batch)
         chain_ready = false;
         const uint32_t Bn = use_chain ? chain_B : Bn0;
-        const bool early = !use_chain && Bn > 0 && early_now(Bn);
         if (Bn > 0 && !use_chain) {
             slot_free(cur ^ 1);
-            if (early) {
-                Batch *gn = &gen[cur ^ 1];
-                const double bound = best_min_score;
-                const bool cut_next = it_next >= lo_start;
-                const BatchBufs *prev = it >= lo_start ? &Q : nullptr; // this batch can publish a record
-                X_.sampler->start(rs_, gn, Bn, cur ^ 1, slot_for(cur ^ 1, Bn), [this, gn, bound, cut_next, prev] {
-                    MP_HIP(hipSetDevice(X_.device));
-                    launch_batch(*gn, bound, cut_next, prev);
-                });
-            } else {
-                X_.sampler->start(rs_, &gen[cur ^ 1], Bn, cur ^ 1, slot_for(cur ^ 1, Bn));
-            }
+            X_.sampler->start(rs_, &gen[cur ^ 1], Bn, cur ^ 1, slot_for(cur ^ 1, Bn));
         }
         auto tw = Clock::now();
         tl_.mark("wait", (long)it);
@@ -2033,10 +1972,7 @@ void Run::run(Model *best, Stats *S) {
             MP_HIP(hipStreamSynchronize(X_.copy_stream));
         }
         bool invalidated = false;
-        bool spec = false; // the sampler holds the post-LO speculation, not the Bn batch
-        uint64_t spec_draws = 0;
-        bool spec_chain = false, spec_chain_launched = false; // ... and the batch after it (make_chain)
-        uint32_t spec_chain_at = 0, spec_chain_B = 0;
+        Speculation sp; // (on: the sampler holds the post-LO speculation, not the Bn batch)
         uint32_t j = 0;
         const bool dumping = model_dump_ || count_dump_;
         for (; j < B; ++j) {
@@ -2128,47 +2064,10 @@ void Run::run(Model *best, Stats *S) {
                             rewind(g, j);
                             ++S->number_lo_iterations;
                             double sc = best_min_score;
-                            const uint32_t at = iter + 1;
-                            // The hook runs on an LO worker beside the steps: it
-                            // gets copies of the loop state it reads -- the streams as rewound
-                            // (the LO draws only from its own copies of the selection stream
-                            // and writes rs_ after LoWorkers::run has returned), the free
-                            // slot, whether a continuation is pending, the pre-LO best (LO
-                            // leaves best_min_model_score alone, src/hybrid_ransac.h:149-155)
-                            // -- and writes only spec / spec_draws, read after the join.
-                            const IterationStream rs_at_lo = rs_;
-                            const int slot = cur ^ 1;
-                            const bool cont_pending = Bn > 0;
-                            const double bound = best_min_score;
-                            Batch *const gs = &gen[slot];
-                            auto predicted = [this, rs_at_lo, slot, cont_pending, bound, gs, at, max_total, speculate,
-                                              lo_start, &grow, &batch_size, &spec, &spec_draws, &make_chain,
-                                              &spec_chain, &spec_chain_at, &spec_chain_B,
-                                              &spec_chain_launched](const Mt19937 &sel_end) {
-                                if (!speculate || at >= max_total) return;
-                                if (cont_pending) X_.sampler->cancel(); // the no-LO continuation
-                                IterationStream from = rs_at_lo;
-                                from.sel = sel_end;
-                                const uint32_t bc = grow(at);
-                                slot_free(slot); // (an early continuation's samples are on the device)
-                                const uint32_t Bs = batch_size(at, sync_batch(bc));
-                                Sampler::Chain ch;
-                                spec_chain = make_chain(at, Bs, slot, bound, &ch, &spec_chain_at, &spec_chain_B);
-                                spec_chain_launched = spec_chain && ch.after != nullptr;
-                                X_.sampler->start(from, gs, Bs, slot, slot_for(slot, Bs),
-                                                  [this, gs, bound, at, lo_start] {
-                                                      // the sampler thread is not bound to the
-                                                      // estimator's device by itself
-                                                      MP_HIP(hipSetDevice(X_.device));
-                                                      launch_batch(*gs, bound, at >= lo_start);
-                                                  },
-                                                  spec_chain ? &ch : nullptr);
-                                spec = true;
-                                spec_draws = sel_end.draws();
-                            };
                             tl_.mark("lo", (long)iter);
-                            local_opt(S->best_solver_type, &best_min, &sc, &S->best_solver_type, predicted);
-                            tl_.mark("lo_end", spec ? 1 : 0);
+                            local_opt(S->best_solver_type, &best_min, &sc, &S->best_solver_type,
+                                      speculation_hook(iter + 1, Bn > 0, &sp));
+                            tl_.mark("lo_end", sp.on ? 1 : 0);
                             if (trace_) std::fprintf(stderr, "[engine] it=%u LO %.17g -> %.17g\n", iter, best_min_score, sc);
                             update_best(sc, best_min, st, &S->best_model_score, best, &S->best_solver_type);
                             lo_here = true;
@@ -2201,7 +2100,6 @@ void Run::run(Model *best, Stats *S) {
                     rs_ = crs;
                     have_next = true;
                     cur ^= 1;
-                    launched = chain_launched;
                 } // (else rs_ stands at the end of this batch)
             } else if (Bn > 0) { // rs_ moves to the end of the drawn batch
                 auto t0 = Clock::now();
@@ -2209,31 +2107,11 @@ void Run::run(Model *best, Stats *S) {
                 have_next = X_.sampler->finish(&rs_);
                 tl_.mark("joined", have_next ? 1 : 0);
                 sample_s_ += secs(t0);
-                if (have_next) {
-                    cur ^= 1;
-                    launched = early; // (the sampler launched it once drawn)
-                }
+                if (have_next) cur ^= 1;
             }
             // (otherwise rs_ stands at the end of this batch)
-        } else if (spec) {
-            have_next = false;
-            if (!done && rs_.sel.draws() == spec_draws) {
-                // the LO ended where predicted: the speculative batch comes next
-                tl_.mark("join_spec");
-                have_next = X_.sampler->finish(&rs_);
-                tl_.mark("joined", have_next ? 1 : 0);
-                if (have_next) {
-                    cur ^= 1;
-                    launched = true;
-                    chain_ready = spec_chain; // (still drawing, maybe: chained() above)
-                    chain_at = spec_chain_at;
-                    chain_B = spec_chain_B;
-                    chain_launched = spec_chain && spec_chain_launched;
-                }
-            } else {
-                X_.sampler->cancel();
-                drain_batches(); // a launched speculation drains
-            }
+        } else if (sp.on) {
+            join_speculation(sp, !done);
         } else {
             if (Bn > 0) X_.sampler->cancel();
             have_next = false;
@@ -2241,7 +2119,7 @@ void Run::run(Model *best, Stats *S) {
         bcur = (int)grow(it);
     }
     if (!done) S->num_iterations_total = it;
-    // (a continuation launched past the end may still be in flight: the next run reuses
+    // (a speculation launched past the end may still be in flight: the next run reuses
     // the buffers)
     X_.sampler->cancel();
     drain_batches();

@@ -92,16 +92,6 @@ struct PairData {
     // CAL: the rays' first two components a = K0^-1 x0, b = K1^-1 x1 (prep_pair_kernel;
     // the score kernel's ray form reads them instead of forming them per trip)
     const double *a0 = nullptr, *a1 = nullptr, *b0 = nullptr, *b1 = nullptr;
-    // Batch gate (nullable): the kernels of a batch launched before the previous batch's
-    // results were read leave at once when that batch published a record (score_batch's
-    // record word holds ~its epoch, gate_hi), i.e. when the host is bound to run LO and
-    // discard this batch (engine.cpp, early continuation)
-    const unsigned long long *gate = nullptr;
-    unsigned gate_hi = 0;
-};
-struct BatchGate {
-    const unsigned long long *word = nullptr;
-    unsigned hi = 0;
 };
 
 // Per-iteration outcome of a batch (score_batch): the iteration's best score

@@ -16,8 +16,7 @@
 // of q) come from balance + elmhes + hqr (EISPACK) on the 15 x 15 block.  Positive
 // real ones (wi == 0) are the candidates u, ascending.
 //
-// This replaces the 16-point DFT of q(u) + Sturm search (group_6pt.h, kept as an A/B
-// path): the DFT loses the digits of small coefficients when the roots span several
+// This replaced the 16-point DFT of q(u) + Sturm search (retired): the DFT loses the digits of small coefficients when the roots span several
 // orders of magnitude (q's coefficients spanned up to 43 orders on random samples)
 // and dropped or shifted roots; on 6000 random samples the deflated eigenvalues
 // agree with a 60-digit evaluation of q's roots in all but one ill-conditioned pair
@@ -38,7 +37,7 @@
 namespace mp {
 namespace {
 
-// Phase timing / counters for tools/eig6_bench.hip (compiled out otherwise): clock
+// Phase timing / counters for a stand-alone bench (compiled out otherwise): clock
 // ticks of balance, elmhes, hqr summed over samples (lane 0), then the QR iterations
 // and balancing passes.
 #ifdef MP_EIG6_PROFILE
@@ -69,7 +68,6 @@ constexpr int kPenStride = 300;
 static_assert(kPenStride == kPtPenStride, "the engine sizes the pencil workspace with kPtPenStride (kernels.h)");
 __global__ void __launch_bounds__(64) pt_pencil6_kernel(PairData D, const int *list, int nlist, const int *samples,
                                                         double *cand, int cand_stride, double *pen) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return; // (uniform: the record word is read by every lane)
     __shared__ double shN[kGrpPerWg][27];
     const int g = threadIdx.x / kGrp, r = threadIdx.x % kGrp;
     const int idx = blockIdx.x * kGrpPerWg + g;
@@ -180,8 +178,7 @@ namespace {
 // wave-uniform (e15_hqr<true>: scalar branches instead of select chains); lane 0 writes.
 template <bool U>
 __global__ void __launch_bounds__(64) pt_eig6_reg_kernel(double *pen, int nlist, int spw, double *cand, int *ncand,
-                                                         int cand_stride, BatchGate gate) {
-    if (batch_cancelled(gate.word, gate.hi)) return;
+                                                         int cand_stride) {
     const int idx = U ? (int)blockIdx.x : (int)(blockIdx.x * spw + threadIdx.x);
     const bool valid = (U || (int)threadIdx.x < spw) && idx < nlist;
     const int sidx = valid ? idx : nlist - 1;

@@ -29,7 +29,7 @@
 namespace mp {
 namespace {
 
-// Phase timing for tools/eig6_bench.hip (compiled out otherwise): wall-clock ticks of
+// Phase timing for a stand-alone bench (compiled out otherwise): wall-clock ticks of
 // the kernel's phases, summed over waves (lane 0)
 #ifdef MP_EIG6_PROFILE
 __device__ unsigned long long e6g_prof[10];
@@ -119,8 +119,7 @@ __device__ __forceinline__ void e6g_null(const double (&g)[NC], unsigned cols, i
     });
 }
 
-__global__ void __launch_bounds__(64) pt_defl6_grp_kernel(double *pen, int nlist, BatchGate gate) {
-    if (batch_cancelled(gate.word, gate.hi)) return;
+__global__ void __launch_bounds__(64) pt_defl6_grp_kernel(double *pen, int nlist) {
     E6G_START;
     const int i = threadIdx.x & 15;
     const int idx = blockIdx.x * 4 + (threadIdx.x >> 4);

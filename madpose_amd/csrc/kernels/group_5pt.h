@@ -340,7 +340,6 @@ __device__ __forceinline__ void pt_roots5_group_core(int bid, int nlist, Load &&
 __device__ __forceinline__ void pt_roots5_group_body(int bid, const PairData &D, const PairConst &C, const int *list,
                                                      int nlist, const int *samples, double *cand, int *ncand,
                                                      int cand_stride) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return; // (uniform: the record word is read by every lane)
     auto load = [&](int idx, double (&b1)[5][3], double (&b2)[5][3]) {
 #pragma clang fp contract(off)
         const int *s = samples + (size_t)list[idx] * kSampleStride;

@@ -5,7 +5,7 @@
 //                     sample (side stream); md_solve<V, ALT> keeps one sample per lane
 //                     for the option-gated paths (scale-only, no shift, alternates)
 //  pt_solve<V>        point minimal solvers in stages: root stage (group_5pt.h /
-//                     group_6pt.h / lane 7pt), tails per root (group_tail.h),
+//                     eig6.h / lane 7pt), tails per root (group_tail.h),
 //                     compaction into model slots
 //  score_batch<V>     THE hot loop: one workgroup per RANSAC iteration; each lane owns
 //                     correspondences i = lane, lane+256, ...; all models of the
@@ -151,7 +151,6 @@ template <int V, bool ALT>
 __global__ void __launch_bounds__(64) md_solve_kernel(PairData D, PairConst C, const int *list, int nlist,
                                                       const int *samples, Model *models, ScoreRec *recs, int *counts,
                                                       int maxm) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return; // (uniform: the record word is read by every lane)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nlist) return;
     const int b = list[idx];
@@ -280,7 +279,6 @@ template <int V, int R>
 __device__ __forceinline__ void md_exact_body(int bid, const PairData &D, const PairConst &C, const int *list,
                                               int nlist, const int *samples, Model *models, ScoreRec *recs,
                                               int *counts, int maxm) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return; // (uniform: the record word is read by every lane)
     using Sys = typename MdxSys<V>::S;
     constexpr int K = MdxSys<V>::K, NR = Sys::NR;
     static_assert(R == 1 || R == 2 || R == 4 || R == 8, "1, 2, 4 or 8 lanes per sample");
@@ -376,7 +374,6 @@ template <int V> struct MdxWs {
 template <int V>
 __device__ __forceinline__ void md_setup_body(int bid, const PairData &D, const PairConst &C, const int *list,
                                               int nlist, const int *samples, double *ws, int *ws_nr, int ld) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return;
     using Sys = typename MdxSys<V>::S;
     constexpr int K = MdxSys<V>::K, NR = Sys::NR, W = MdxWs<V>::W;
     const int idx = bid * 64 + (int)threadIdx.x;
@@ -398,7 +395,6 @@ template <int V>
 __device__ __forceinline__ void md_root_body(int bid, const PairData &D, const PairConst &C, const int *list, int nlist,
                                              const int *samples, const double *ws, const int *ws_nr, int ld,
                                              Model *models, ScoreRec *recs, int *counts, int maxm) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return;
     using Sys = typename MdxSys<V>::S;
     constexpr int K = MdxSys<V>::K, NR = Sys::NR, W = MdxWs<V>::W, R = NR;
     const int g = threadIdx.x / R, r = threadIdx.x % R;
@@ -572,7 +568,6 @@ template <> struct PtTraits<kTF> {
 // oracle's relpose_7pt operation for operation, oracle/src/pt_poselib.cpp)
 __global__ void __launch_bounds__(64) pt_roots7_kernel(PairData D, const int *list, int nlist, const int *samples,
                                                        double *cand, int *ncand) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return; // (uniform: the record word is read by every lane)
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= nlist) return;
     const int *s = samples + (size_t)list[idx] * kSampleStride;
@@ -600,8 +595,7 @@ __global__ void __launch_bounds__(64) pt_roots7_kernel(PairData D, const int *li
 template <int V>
 __global__ void __launch_bounds__(64) pt_compact_kernel(PairConst C, const int *list, int nlist, const int *ncand,
                                                         const Model *slots, const int *valid, Model *models,
-                                                        ScoreRec *recs, int *counts, int maxm, BatchGate gate) {
-    if (batch_cancelled(gate.word, gate.hi)) return;
+                                                        ScoreRec *recs, int *counts, int maxm) {
     using T = PtTraits<V>;
     constexpr int kSlots = T::kPosesPerRoot * T::kRoots;
     constexpr int G = kSlots <= 4 ? 4 : 32;
@@ -703,7 +697,6 @@ template <int V, int MAXM, bool FAST, bool EXIT>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(FAST ? 5 : 1)))
 score_batch_kernel(PairData D, PairConst C, const ScoreRec *__restrict__ recs, const int *__restrict__ counts,
                    double *scores, IterResult *res, ScoreBound sb) {
-    if (batch_cancelled(D.gate, D.gate_hi)) return; // (uniform: the record word is read by every lane)
     const int b = blockIdx.x;
     const int nm = counts[b];
     if (nm == 0) {
@@ -1278,14 +1271,12 @@ static void launch_sf_eig(hipStream_t s, const PairData &D, const int *list, int
                           double *cand, int *ncand, double *pen) {
     pt_pencil6_kernel<<<(nlist + kGrpPerWg - 1) / kGrpPerWg, 64, 0, s>>>(D, list, nlist, samples, cand, kCandStride,
                                                                          pen);
-    const BatchGate gate{D.gate, D.gate_hi};
-    pt_defl6_grp_kernel<<<(nlist + 3) / 4, 64, 0, s>>>(pen, nlist, gate);
+    pt_defl6_grp_kernel<<<(nlist + 3) / 4, 64, 0, s>>>(pen, nlist);
     const int spw = eig_spw(nlist);
     if (spw == 1)
-        pt_eig6_reg_kernel<true><<<nlist, 64, 0, s>>>(pen, nlist, 1, cand, ncand, kCandStride, gate);
+        pt_eig6_reg_kernel<true><<<nlist, 64, 0, s>>>(pen, nlist, 1, cand, ncand, kCandStride);
     else
-        pt_eig6_reg_kernel<false><<<(nlist + spw - 1) / spw, 64, 0, s>>>(pen, nlist, spw, cand, ncand, kCandStride,
-                                                                         gate);
+        pt_eig6_reg_kernel<false><<<(nlist + spw - 1) / spw, 64, 0, s>>>(pen, nlist, spw, cand, ncand, kCandStride);
 }
 
 bool solve_fusable(const PairConst &C) {
@@ -1316,7 +1307,7 @@ hipError_t launch_solve_fused(hipStream_t s, const PairData &D, const PairConst 
         if (npt > 0) {
             constexpr int kCompactG = 32; // (PtTraits<kCal>: 2 poses x 10 roots > 4)
             pt_compact_kernel<kCal><<<(int)(((size_t)npt * kCompactG + 63) / 64), 64, 0, s>>>(
-                C, pt_list, npt, W.ncand, W.slots, W.valid, models, recs, counts, maxm, BatchGate{D.gate, D.gate_hi});
+                C, pt_list, npt, W.ncand, W.slots, W.valid, models, recs, counts, maxm);
         }
         return hipGetLastError();
     }
@@ -1358,7 +1349,7 @@ hipError_t launch_pt_solve(hipStream_t s, const PairData &D, const PairConst &C,
                                                                                 samples, W.slots, W.valid);
         constexpr int kCompactG = PtTraits<v>::kPosesPerRoot * PtTraits<v>::kRoots <= 4 ? 4 : 32;
         pt_compact_kernel<v><<<(int)(((size_t)nlist * kCompactG + 63) / 64), 64, 0, s>>>(
-            C, list, nlist, W.ncand, W.slots, W.valid, models, recs, counts, maxm, BatchGate{D.gate, D.gate_hi});
+            C, list, nlist, W.ncand, W.slots, W.valid, models, recs, counts, maxm);
         return hipGetLastError();
     });
 }

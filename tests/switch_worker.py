@@ -36,7 +36,7 @@ def main():
         cam0, cam1 = (p["K0"], p["K1"]) if variant == 0 else (p["pp0"], p["pp1"])
         pose, st = FN[variant](p["x0"], p["x1"], p["depth0"], p["depth1"], p["min_depth"], cam0, cam1, o, c)
         out.append(record(variant, pose, st))
-    # several estimators on the device at once (the early continuation's other regime)
+    # several estimators on the device at once (active_runs() > 1: the LO workers do not spin)
     pairs = [synthetic.scannet_pair(s) for s in range(4)]
     o, c = synthetic.example_options("shared_focal", iterations=1000)
     for pose, st in api.estimate_batch(1, pairs, o, c, num_streams=4):

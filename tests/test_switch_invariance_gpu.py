@@ -1,7 +1,6 @@
 """The engine's performance switches change no result: the full-size estimator cases
 and four pairs in flight, each switch setting in a fresh process (the engine reads them
-once), compared field by field with the default run to the last bit -- the early
-continuation on while alone and always (MADPOSE_EARLY_CONT, §2 step 7 of DESIGN.md), the
+once), compared field by field with the default run to the last bit -- the
 exact MD solvers on one or two lanes per sample instead of the defaults (MADPOSE_MDX_R; cal
 and tf 4, sf 2), the scalar
 batch drawing instead of AVX-512 (MADPOSE_SAMPLER_SIMD), the 15x15 QR packed 16
@@ -11,7 +10,7 @@ stage on two streams instead of one fused launch (MADPOSE_SOLVE_FUSE), score_bat
 one trip per loop step instead of two between early-exit checks (MADPOSE_SCORE_PAIR), the
 post-LO speculation predicted after the LO prefix instead of before it
 (MADPOSE_LO_EARLY_HOOK) or not at all (MADPOSE_LO_SPECULATE), and without the batch after
-it drawn (MADPOSE_LO_CHAIN) or launched (MADPOSE_LO_CHAIN_LAUNCH) in the same job; the
+it drawn in the same job (MADPOSE_LO_CHAIN); the
 scoring without its exact early exit (MADPOSE_SCORE_EXIT) or record skip
 (MADPOSE_RECORD_SKIP), with an exit check after every trip (MADPOSE_SCORE_CHECK), and the
 fused MD + 5pt launch for no batch or only up to 8192 iterations instead of every batch
@@ -31,12 +30,10 @@ import madpose
 pytestmark = pytest.mark.gpu
 
 WORKER = os.path.join(os.path.dirname(os.path.abspath(__file__)), "switch_worker.py")
-SETTINGS = {"early_alone": {"MADPOSE_EARLY_CONT": "1"}, "early_always": {"MADPOSE_EARLY_CONT": "2"},
-            "mdx_one_lane": {"MADPOSE_MDX_R": "1"}, "mdx_two_lanes": {"MADPOSE_MDX_R": "2"}, "sampler_scalar": {"MADPOSE_SAMPLER_SIMD": "0"},
+SETTINGS = {"mdx_one_lane": {"MADPOSE_MDX_R": "1"}, "mdx_two_lanes": {"MADPOSE_MDX_R": "2"}, "sampler_scalar": {"MADPOSE_SAMPLER_SIMD": "0"},
             "eig_packed": {"MADPOSE_EIG_WAVES": "16"}, "eig_waves_1024": {"MADPOSE_EIG_WAVES": "1024"}, "draw_by_draw": {"MADPOSE_SAMPLER_TWO_PASS": "0"},
-            "solve_unfused": {"MADPOSE_SOLVE_FUSE": "0"}, "early_big": {"MADPOSE_EARLY_CONT": "3"}, "lo_late_hook": {"MADPOSE_LO_EARLY_HOOK": "0"},
+            "solve_unfused": {"MADPOSE_SOLVE_FUSE": "0"}, "lo_late_hook": {"MADPOSE_LO_EARLY_HOOK": "0"},
             "lo_no_speculation": {"MADPOSE_LO_SPECULATE": "0"}, "lo_no_chain": {"MADPOSE_LO_CHAIN": "0"},
-            "lo_chain_launched": {"MADPOSE_LO_CHAIN_LAUNCH": "1"},
             "score_single_trips": {"MADPOSE_SCORE_PAIR": "0"},
             "score_no_exit": {"MADPOSE_SCORE_EXIT": "0"}, "no_record_skip": {"MADPOSE_RECORD_SKIP": "0"},
             "score_check_every_trip": {"MADPOSE_SCORE_CHECK": "1,1"},
