@@ -267,6 +267,29 @@ int mp_debug_pt_roots(int variant, int impl, int64_t ns, const double *pts0, con
 int mp_relpose_6pt_shared_focal(const double *x0, const double *x1, mp_model *out, int max_out, int device);
 int mp_relpose_7pt_two_focal(const double *x0, const double *x1, mp_model *out, int max_out, int device);
 
+/* The standalone solvers over ns samples per call.  Inputs are sample-major and inside
+ * a sample exactly the single-sample layout: x_homo / y_homo ns x K x 3 (K = 3
+ * calibrated, 4 otherwise), depths ns x K; mp_relpose_batch kind 0 (5pt): unit bearings
+ * ns x 5 x 3, kind 1 / 2 (6pt shared focal / 7pt two focal): normalized 2-D points ns x 6
+ * x 2 / ns x 7 x 2.  Outputs: mp_solve_scale_and_shift_batch ns x 8 rows of width 4 / 5 /
+ * 6, mp_solve_scale_shift_pose_batch ns x 8 models (alt 0: the default solvers, 1 / 2 as
+ * mp_solve_scale_shift_pose_alt), mp_relpose_batch ns x 16 models, within a sample in the
+ * single-sample entry's order; counts[s] = that entry's return value for sample s (at
+ * most the slot count), the slots from counts[s] on are zero.  Every row equals the
+ * single-sample entry's result bit for bit.  The batch runs in rounds of `chunk` samples
+ * on one set of device buffers (chunk bounds their size; 0 = MP_SOLVE_BATCH_CHUNK).
+ * ns == 0 returns MP_OK without touching the device; ns < 0 or ns > 2^22, null pointers,
+ * a bad variant / alt / kind or chunk < 0 give MP_EINVAL.  Returns MP_OK or a code. */
+#define MP_SOLVE_BATCH_CHUNK 32768
+int mp_solve_scale_and_shift_batch(int variant, int64_t ns, const double *x_homo, const double *y_homo,
+                                   const double *depth_x, const double *depth_y, double *out, int32_t *counts,
+                                   int64_t chunk, int device);
+int mp_solve_scale_shift_pose_batch(int variant, int alt, int64_t ns, const double *x_homo, const double *y_homo,
+                                    const double *depth_x, const double *depth_y, mp_model *out, int32_t *counts,
+                                    int64_t chunk, int device);
+int mp_relpose_batch(int kind, int64_t ns, const double *x0, const double *x1, mp_model *out, int32_t *counts,
+                     int64_t chunk, int device);
+
 /* Test hooks for the host-side random streams (no device needed).
  * mp_debug_random_stream: kind 0 raw mt19937 words, 1 uniform_int(a, b),
  * 2 uniform_real(0, b), 3 uniform_int(i % 300, 300 + i % 17) for i = 0..count-1.

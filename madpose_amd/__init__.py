@@ -28,18 +28,22 @@ from .api import (  # noqa: F401
     get_depths_batch,
     pose_auc_batch,
     pose_eval_batch,
+    poses_from_models,
     profile_enable,
     profile_read,
     profile_reset,
     relpose_5pt,
     relpose_6pt_shared_focal,
     relpose_7pt_two_focal,
+    relpose_batch,
     score_models,
     set_device,
     solve_scale_and_shift,
+    solve_scale_and_shift_batch,
     solve_scale_and_shift_shared_focal,
     solve_scale_and_shift_two_focal,
     solve_scale_shift_pose,
+    solve_scale_shift_pose_batch,
     solve_scale_shift_pose_shared_focal,
     solve_scale_shift_pose_ours,
     solve_scale_shift_pose_shared_focal_ours,

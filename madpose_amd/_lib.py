@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(_HERE, "lib", "libmadpose_mi355x" + (f"_{_VARIANT}" if _
 
 MP_OK, MP_EINVAL, MP_EDEVICE = 0, 1, 2
 CALIBRATED, SHARED_FOCAL, TWO_FOCAL, SCALE_ONLY = 0, 1, 2, 3
+# the batched solvers (mp_*_batch): samples per call, samples per round when chunk == 0
+SOLVE_BATCH_MAX, SOLVE_BATCH_CHUNK = 1 << 22, 32768
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -173,6 +175,15 @@ EXPORTS = {
                                           ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
     "mp_debug_pt_roots": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p,
                                          c_double_p, ctypes.POINTER(ctypes.c_int32), ctypes.c_int]),
+    "mp_solve_scale_and_shift_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p,
+                                                      c_double_p, c_double_p, c_double_p, c_int32_p,
+                                                      ctypes.c_int64, ctypes.c_int]),
+    "mp_solve_scale_shift_pose_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int64, c_double_p,
+                                                       c_double_p, c_double_p, c_double_p,
+                                                       ctypes.POINTER(mp_model), c_int32_p, ctypes.c_int64,
+                                                       ctypes.c_int]),
+    "mp_relpose_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p,
+                                        ctypes.POINTER(mp_model), c_int32_p, ctypes.c_int64, ctypes.c_int]),
     "mp_relpose_6pt_shared_focal": (ctypes.c_int, [c_double_p, c_double_p, ctypes.POINTER(mp_model), ctypes.c_int,
                                                    ctypes.c_int]),
     "mp_relpose_7pt_two_focal": (ctypes.c_int, [c_double_p, c_double_p, ctypes.POINTER(mp_model), ctypes.c_int,

@@ -665,6 +665,111 @@ def solve_scale_shift_pose_two_focal_4p4d(x_homo, y_homo, depth_x, depth_y):
     return _solve_pose(L.TWO_FOCAL, x_homo, y_homo, depth_x, depth_y, alt=2)
 
 
+# ---------------------------------------------------------------------------
+# the standalone solvers over many samples per call (mp_*_batch)
+def _batch_array(a, tail, name):
+    """a as a float64 array of shape (B,) + tail (no copy yet: B is checked first)"""
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 1 + len(tail) or tuple(a.shape[1:]) != tuple(tail):
+        raise ValueError(f"{name} must have shape (B, {', '.join(str(t) for t in tail)}), got {a.shape}")
+    return a
+
+
+def _batch_common(arrays, chunk):
+    B = arrays[0].shape[0]
+    if any(a.shape[0] != B for a in arrays):
+        raise ValueError("the arrays must hold the same number of samples")
+    if B > L.SOLVE_BATCH_MAX:
+        raise ValueError(f"at most 2^22 samples per call, got {B}")
+    if int(chunk) != chunk or chunk < 0:
+        raise ValueError("chunk must be a non-negative integer (0: the default)")
+    return B
+
+
+def _md_batch_inputs(variant, x_homo, y_homo, depth_x, depth_y, chunk):
+    if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL):
+        raise ValueError("variant must be 0 (calibrated), 1 (shared focal) or 2 (two focal)")
+    k = 3 if variant == L.CALIBRATED else 4
+    arrs = [_batch_array(x_homo, (k, 3), "x_homo"), _batch_array(y_homo, (k, 3), "y_homo"),
+            _batch_array(depth_x, (k,), "depth_x"), _batch_array(depth_y, (k,), "depth_y")]
+    B = _batch_common(arrs, chunk)
+    return B, [np.ascontiguousarray(a) for a in arrs] if B else arrs
+
+
+def solve_scale_and_shift_batch(variant, x_homo, y_homo, depth_x, depth_y, chunk=0, device=None):
+    """solve_scale_and_shift{,_shared_focal,_two_focal} (variant 0 / 1 / 2) over B samples
+    in device launches that fill the GPU.  x_homo, y_homo: (B, K, 3) homogeneous points, one
+    per row (K = 3 calibrated, 4 otherwise); depth_x, depth_y: (B, K).  Returns (sols, counts):
+    sols (B, 8, w) with w = 4 / 5 / 6, rows in the single-sample function's order, rows from
+    counts[b] on zero.  Every row equals the single-sample result bit for bit.  chunk:
+    samples per launch round (bounds device memory; 0 = the default)."""
+    B, (x, y, dx, dy) = _md_batch_inputs(variant, x_homo, y_homo, depth_x, depth_y, chunk)
+    w = [4, 5, 6][variant]
+    sols = np.zeros((B, 8, w))
+    counts = np.zeros(B, dtype=np.int32)
+    if B:
+        L.check(L.lib().mp_solve_scale_and_shift_batch(variant, B, _dp(x), _dp(y), _dp(dx), _dp(dy), _dp(sols),
+                                                       counts.ctypes.data_as(L.c_int32_p), int(chunk),
+                                                       _DEFAULT_DEVICE if device is None else int(device)))
+    return sols, counts
+
+
+def solve_scale_shift_pose_batch(variant, x_homo, y_homo, depth_x, depth_y, alt=0, chunk=0, device=None):
+    """solve_scale_shift_pose{,_shared_focal,_two_focal} over B samples (inputs as
+    solve_scale_and_shift_batch); alt 1: the _ours solvers, alt 2: _two_focal_4p4d (variant
+    2 only).  Returns (models, counts): models (B, 8, 17) float64 in mp_model field order
+    (R 9, t 3, scale, offset0, offset1, focal0, focal1; poses_from_models converts a
+    sample's rows), slots from counts[b] on zero; bit-identical to the single-sample calls."""
+    if alt not in (0, 1, 2) or (alt == 2 and variant != L.TWO_FOCAL):
+        raise ValueError("alt must be 0, 1 (use_ours) or 2 (use_4p4d, two-focal only)")
+    B, (x, y, dx, dy) = _md_batch_inputs(variant, x_homo, y_homo, depth_x, depth_y, chunk)
+    models = np.zeros((B, 8, 17))
+    counts = np.zeros(B, dtype=np.int32)
+    if B:
+        L.check(L.lib().mp_solve_scale_shift_pose_batch(variant, int(alt), B, _dp(x), _dp(y), _dp(dx), _dp(dy),
+                                                        models.ctypes.data_as(ctypes.POINTER(L.mp_model)),
+                                                        counts.ctypes.data_as(L.c_int32_p), int(chunk),
+                                                        _DEFAULT_DEVICE if device is None else int(device)))
+    return models, counts
+
+
+def relpose_batch(kind, x0, x1, chunk=0, device=None):
+    """relpose_5pt (kind 0; x0, x1: (B, 5, 3) unit bearings), relpose_6pt_shared_focal (1;
+    (B, 6, 2) normalized points) or relpose_7pt_two_focal (2; (B, 7, 2)) over B samples.
+    Returns (models, counts): models (B, 16, 17) as solve_scale_shift_pose_batch returns
+    them, bit-identical to the single-sample calls."""
+    if kind not in (0, 1, 2):
+        raise ValueError("kind must be 0 (5pt), 1 (6pt shared focal) or 2 (7pt two focal)")
+    tail = [(5, 3), (6, 2), (7, 2)][kind]
+    arrs = [_batch_array(x0, tail, "x0"), _batch_array(x1, tail, "x1")]
+    B = _batch_common(arrs, chunk)
+    models = np.zeros((B, 16, 17))
+    counts = np.zeros(B, dtype=np.int32)
+    if B:
+        a, b = (np.ascontiguousarray(v) for v in arrs)
+        L.check(L.lib().mp_relpose_batch(kind, B, _dp(a), _dp(b), models.ctypes.data_as(ctypes.POINTER(L.mp_model)),
+                                         counts.ctypes.data_as(L.c_int32_p), int(chunk),
+                                         _DEFAULT_DEVICE if device is None else int(device)))
+    return models, counts
+
+
+def poses_from_models(models_rows, variant):
+    """The rows of one sample's models (n x 17, e.g. models[b, :counts[b]]) as the pose
+    objects the single-sample functions return (variant 0 / 1 / 2: PoseScaleOffset /
+    ...SharedFocal / ...TwoFocal)."""
+    if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL):
+        raise ValueError("variant must be 0 (calibrated), 1 (shared focal) or 2 (two focal)")
+    rows = np.ascontiguousarray(np.asarray(models_rows, dtype=np.float64))
+    if rows.ndim != 2 or rows.shape[1] != 17:
+        raise ValueError(f"models_rows must have shape (n, 17), got {rows.shape}")
+    out = []
+    for row in rows:
+        m = L.mp_model()
+        ctypes.memmove(ctypes.byref(m), row.ctypes.data, ctypes.sizeof(m))
+        out.append(_model_from_c(m, variant))
+    return out
+
+
 def score_models(variant, x0, x1, depth0, depth1, cam0, cam1, options, est_config, models, with_errors=False,
                  host_lo=False, fast_bounds=None):
     """Device ScoreModel over explicit models given in problem units (tests / diagnostics).

@@ -279,6 +279,34 @@ int mp_solve_scale_shift_pose_alt(int variant, int alt, const double *x_homo, co
     return r <= -1000 ? -(r + 1000) : -r;
 }
 
+int mp_solve_scale_and_shift_batch(int variant, int64_t ns, const double *x_homo, const double *y_homo,
+                                   const double *depth_x, const double *depth_y, double *out, int32_t *counts,
+                                   int64_t chunk, int device) {
+    return guarded([&]() {
+        mp::solve_md_batch(variant, 0, false, ns, x_homo, y_homo, depth_x, depth_y, out, nullptr, counts, chunk, device);
+        return MP_OK;
+    });
+}
+
+int mp_solve_scale_shift_pose_batch(int variant, int alt, int64_t ns, const double *x_homo, const double *y_homo,
+                                    const double *depth_x, const double *depth_y, mp_model *out, int32_t *counts,
+                                    int64_t chunk, int device) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::Model) == sizeof(mp_model), "model layout");
+        mp::solve_md_batch(variant, alt, true, ns, x_homo, y_homo, depth_x, depth_y, nullptr,
+                           reinterpret_cast<mp::Model *>(out), counts, chunk, device);
+        return MP_OK;
+    });
+}
+
+int mp_relpose_batch(int kind, int64_t ns, const double *x0, const double *x1, mp_model *out, int32_t *counts,
+                     int64_t chunk, int device) {
+    return guarded([&]() {
+        mp::relpose_batch(kind, ns, x0, x1, reinterpret_cast<mp::Model *>(out), counts, chunk, device);
+        return MP_OK;
+    });
+}
+
 extern "C++" {
 namespace {
 // the shared argument handling of mp_score_models and mp_debug_lo_sweep: `sweep`

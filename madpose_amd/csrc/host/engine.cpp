@@ -48,6 +48,7 @@
 #include "env.h"
 #include "lo_sweep.h"
 #include "rng.h"
+#include "solve_batch_pack.h"
 
 namespace mp {
 
@@ -437,6 +438,21 @@ struct DeviceCtx {
     // may already hold the next batch)
     hipStream_t md_stream = nullptr, copy_stream = nullptr;
     std::unique_ptr<Sampler> sampler;               // created on first use
+    // one block for the rounds of the batched minimal solvers (solve_md_batch,
+    // relpose_batch), grown on demand and kept with the context; not sized by ensure()
+    char *d_solve = nullptr;
+    size_t solve_cap = 0;
+    char *solve_block(size_t bytes) {
+        if (bytes > solve_cap) {
+            MP_HIP(hipStreamSynchronize(stream));
+            if (d_solve) MP_HIP(hipFree(d_solve));
+            d_solve = nullptr;
+            solve_cap = 0;
+            MP_HIP(hipMalloc(&d_solve, bytes));
+            solve_cap = bytes;
+        }
+        return d_solve;
+    }
 
     void free_all() {
         hipSetDevice(device);
@@ -2541,6 +2557,40 @@ int solve_point_direct(int kind, const double *x1, const double *x2, Model *pose
     return hn;
 }
 
+// The pseudo-pair of ns point samples of K normalized 2-D points each (pts*: ns x K x 2),
+// as launch_pt_roots reads a pair: one correspondence per sample point (host: the eight
+// PairData arrays x0u x0v x1u x1v d0 d1 r0 r1 of np = K ns entries), sample s = points
+// K s .. K s + K - 1 (smp, kSampleStride ints each), every sample listed.
+static void pt_pseudo_pair(int K, int64_t ns, const double *pts0, const double *pts1, std::vector<double> &host,
+                           std::vector<int> &smp, std::vector<int> &list) {
+    const int64_t np = K * ns;
+    host.resize(8 * (size_t)np);
+    for (int64_t i = 0; i < np; ++i) {
+        host[i] = pts0[2 * i];
+        host[np + i] = pts0[2 * i + 1];
+        host[2 * np + i] = pts1[2 * i];
+        host[3 * np + i] = pts1[2 * i + 1];
+        host[4 * np + i] = host[5 * np + i] = 1.0;
+        host[6 * np + i] = 1.0 / std::sqrt(pts0[2 * i] * pts0[2 * i] + pts0[2 * i + 1] * pts0[2 * i + 1] + 1.0);
+        host[7 * np + i] = 1.0 / std::sqrt(pts1[2 * i] * pts1[2 * i] + pts1[2 * i + 1] * pts1[2 * i + 1] + 1.0);
+    }
+    smp.assign(8 * (size_t)ns, 0);
+    list.resize((size_t)ns);
+    for (int64_t s = 0; s < ns; ++s) {
+        list[s] = (int)s;
+        for (int j = 0; j < K; ++j) smp[8 * s + j] = (int)(K * s + j);
+    }
+}
+// its device views: identity intrinsics, the arrays at d_pair (8 np doubles)
+static void pt_pseudo_views(int variant, int64_t np, double *d_pair, PairData *D, PairConst *C) {
+    *D = PairData{d_pair, d_pair + np, d_pair + 2 * np, d_pair + 3 * np, d_pair + 4 * np, d_pair + 5 * np,
+                  d_pair + 6 * np, d_pair + 7 * np};
+    *C = PairConst{};
+    C->variant = variant;
+    C->n = (int)np;
+    for (int k = 0; k < 9; ++k) C->K0[k] = C->K1[k] = C->K0i[k] = C->K1i[k] = (k % 4 == 0) ? 1.0 : 0.0;
+}
+
 void debug_pt_roots(int variant, int64_t ns, const double *pts0, const double *pts1, double *cand, int *ncand,
                     int device) {
     if (variant != kCal && variant != kSF && variant != kTF)
@@ -2551,21 +2601,9 @@ void debug_pt_roots(int variant, int64_t ns, const double *pts0, const double *p
     const int K = variant == kCal ? 5 : (variant == kSF ? 6 : 7);
     const int64_t np = K * ns;
     // one correspondence per sample point, identity intrinsics, sample s = points Ks..Ks+K-1
-    std::vector<double> host(8 * (size_t)np);
-    for (int64_t i = 0; i < np; ++i) {
-        host[i] = pts0[2 * i];
-        host[np + i] = pts0[2 * i + 1];
-        host[2 * np + i] = pts1[2 * i];
-        host[3 * np + i] = pts1[2 * i + 1];
-        host[4 * np + i] = host[5 * np + i] = 1.0;
-        host[6 * np + i] = 1.0 / std::sqrt(pts0[2 * i] * pts0[2 * i] + pts0[2 * i + 1] * pts0[2 * i + 1] + 1.0);
-        host[7 * np + i] = 1.0 / std::sqrt(pts1[2 * i] * pts1[2 * i] + pts1[2 * i + 1] * pts1[2 * i + 1] + 1.0);
-    }
-    std::vector<int> smp(8 * (size_t)ns, 0), list(ns);
-    for (int64_t s = 0; s < ns; ++s) {
-        list[s] = (int)s;
-        for (int j = 0; j < K; ++j) smp[8 * s + j] = (int)(K * s + j);
-    }
+    std::vector<double> host;
+    std::vector<int> smp, list;
+    pt_pseudo_pair(K, ns, pts0, pts1, host, smp, list);
     DevArray<double> d_pair_a(host.size()), d_cand_a(kPtCandStride * (size_t)ns);
     DevArray<int> d_smp_a(smp.size()), d_list_a(list.size()), d_n_a((size_t)ns);
     double *d_pair = d_pair_a.p, *d_cand = d_cand_a.p;
@@ -2574,17 +2612,152 @@ void debug_pt_roots(int variant, int64_t ns, const double *pts0, const double *p
     MP_HIP(hipMemcpyAsync(d_smp, smp.data(), sizeof(int) * smp.size(), hipMemcpyHostToDevice, X.stream));
     MP_HIP(hipMemcpyAsync(d_list, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice, X.stream));
     MP_HIP(hipMemsetAsync(d_cand, 0, sizeof(double) * kPtCandStride * (size_t)ns, X.stream));
-    PairData D{d_pair, d_pair + np, d_pair + 2 * np, d_pair + 3 * np, d_pair + 4 * np, d_pair + 5 * np,
-               d_pair + 6 * np, d_pair + 7 * np};
-    PairConst C{};
-    C.variant = variant;
-    C.n = (int)np;
-    for (int k = 0; k < 9; ++k) C.K0[k] = C.K1[k] = C.K0i[k] = C.K1i[k] = (k % 4 == 0) ? 1.0 : 0.0;
+    PairData D;
+    PairConst C;
+    pt_pseudo_views(variant, np, d_pair, &D, &C);
     DevArray<double> d_pen(variant == kSF ? (size_t)ns * kPtPenStride : 1);
     MP_HIP(launch_pt_roots(X.stream, D, C, d_list, (int)ns, d_smp, d_cand, d_n, d_pen.p));
     MP_HIP(hipMemcpyAsync(cand, d_cand, sizeof(double) * kPtCandStride * (size_t)ns, hipMemcpyDeviceToHost, X.stream));
     MP_HIP(hipMemcpyAsync(ncand, d_n, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, X.stream));
     MP_HIP(hipStreamSynchronize(X.stream));
+}
+
+// ---- the minimal solvers over many raw samples (mp_*_batch) ----
+// A batch runs in rounds of at most `chunk` samples (host/solve_batch_pack.h); every
+// round reuses the context's block (DeviceCtx::solve_block), carved below.
+namespace {
+struct Carver {
+    char *base;
+    size_t off = 0;
+    template <class T> T *take(size_t n) {
+        off = (off + 255) & ~size_t(255);
+        T *r = reinterpret_cast<T *>(base + off);
+        off += sizeof(T) * n;
+        return r;
+    }
+};
+void check_batch_args(int64_t ns, int64_t chunk) {
+    if (ns < 0 || ns > kSolveBatchMax) throw std::invalid_argument("the number of samples must be in [0, 2^22]");
+    if (chunk < 0) throw std::invalid_argument("chunk must not be negative (0: the default)");
+}
+} // namespace
+
+void solve_md_batch(int variant, int alt, bool pose, int64_t ns, const double *x, const double *y, const double *dx,
+                    const double *dy, double *sols, Model *poses, int32_t *counts, int64_t chunk, int device) {
+    if (variant != kCal && variant != kSF && variant != kTF) throw std::invalid_argument("bad variant");
+    if (alt < 0 || alt > 2 || (alt == 2 && variant != kTF))
+        throw std::invalid_argument("alt must be 0, 1 (use_ours) or 2 (use_4p4d, two-focal only)");
+    if (alt != 0 && !pose) throw std::invalid_argument("the alternates return poses only");
+    check_batch_args(ns, chunk);
+    if (ns == 0) return;
+    if (!x || !y || !dx || !dy || !counts || (pose ? !poses : !sols)) throw std::invalid_argument("bad arguments");
+    CtxLease lease(device);
+    DeviceCtx &X = *lease.c;
+    const int K = variant == kCal ? 3 : 4, w = variant == kCal ? 4 : (variant == kSF ? 5 : 6);
+    const int64_t cmax = solve_batch_chunk(ns, chunk), ldmax = solve_batch_ld(cmax);
+    const size_t out_bytes = pose ? sizeof(Model) * 8 : sizeof(double) * 8 * w; // per sample
+    double *d_in = nullptr;
+    char *d_out = nullptr;
+    int *d_n = nullptr;
+    auto carve = [&](char *base) {
+        Carver c{base};
+        d_in = c.take<double>((size_t)md_rows(K) * ldmax);
+        d_out = c.take<char>(out_bytes * cmax);
+        d_n = c.take<int>((size_t)cmax);
+        return c.off;
+    };
+    carve(X.solve_block(carve(nullptr)));
+    std::vector<double> hin((size_t)md_rows(K) * ldmax, 0.0);
+    char *out = pose ? reinterpret_cast<char *>(poses) : reinterpret_cast<char *>(sols);
+    for (int64_t r = 0, nr = solve_batch_rounds(ns, chunk); r < nr; ++r) {
+        int64_t s0, cnt;
+        solve_batch_round(ns, chunk, r, &s0, &cnt);
+        const int64_t ld = solve_batch_ld(cnt);
+        pack_md_soa(K, s0, cnt, ld, x, y, dx, dy, hin.data());
+        MP_HIP(hipMemcpyAsync(d_in, hin.data(), sizeof(double) * md_rows(K) * ld, hipMemcpyHostToDevice, X.stream));
+        MP_HIP(hipMemsetAsync(d_out, 0, out_bytes * cnt, X.stream));
+        MP_HIP(launch_sb_md(X.stream, variant, alt, pose, d_in, (int)ld, (int)cnt, reinterpret_cast<double *>(d_out),
+                            reinterpret_cast<Model *>(d_out), d_n));
+        MP_HIP(hipMemcpyAsync(out + out_bytes * s0, d_out, out_bytes * cnt, hipMemcpyDeviceToHost, X.stream));
+        MP_HIP(hipMemcpyAsync(counts + s0, d_n, sizeof(int) * cnt, hipMemcpyDeviceToHost, X.stream));
+        MP_HIP(hipStreamSynchronize(X.stream)); // (hin is packed again for the next round)
+    }
+}
+
+void relpose_batch(int kind, int64_t ns, const double *x0, const double *x1, Model *poses, int32_t *counts,
+                   int64_t chunk, int device) {
+    if (kind < 0 || kind > 2) throw std::invalid_argument("point solver kind must be 0, 1 or 2");
+    check_batch_args(ns, chunk);
+    if (ns == 0) return;
+    if (!x0 || !x1 || !poses || !counts) throw std::invalid_argument("bad arguments");
+    CtxLease lease(device);
+    DeviceCtx &X = *lease.c;
+    const int K = kind == 0 ? 5 : (kind == 1 ? 6 : 7);
+    const int per = kind == 0 ? 15 : 2 * K; // doubles of a sample per image
+    const int64_t cmax = solve_batch_chunk(ns, chunk), ldmax = solve_batch_ld(cmax);
+    double *d_in = nullptr, *d_cand = nullptr, *d_pen = nullptr, *d_pair = nullptr, *d_F = nullptr;
+    int *d_ncand = nullptr, *d_n = nullptr, *d_smp = nullptr, *d_list = nullptr;
+    Model *d_poses = nullptr;
+    auto carve = [&](char *base) {
+        Carver c{base};
+        d_in = c.take<double>(kind == 2 ? 28 * (size_t)ldmax : 2 * (size_t)per * cmax);
+        d_poses = c.take<Model>(16 * (size_t)cmax);
+        d_n = c.take<int>((size_t)cmax);
+        if (kind != 2) {
+            d_cand = c.take<double>((size_t)kPtCandStride * cmax);
+            d_ncand = c.take<int>((size_t)cmax);
+        }
+        if (kind == 1) {
+            d_pen = c.take<double>((size_t)kPtPenStride * cmax);
+            d_pair = c.take<double>(8 * (size_t)K * cmax);
+            d_smp = c.take<int>(8 * (size_t)cmax);
+            d_list = c.take<int>((size_t)cmax);
+        }
+        if (kind == 2) d_F = c.take<double>(27 * (size_t)ldmax);
+        return c.off;
+    };
+    carve(X.solve_block(carve(nullptr)));
+    std::vector<double> hin(kind == 2 ? 28 * (size_t)ldmax : 2 * (size_t)per * cmax, 0.0), hpair;
+    std::vector<int> smp, list;
+    for (int64_t r = 0, nr = solve_batch_rounds(ns, chunk); r < nr; ++r) {
+        int64_t s0, cnt;
+        solve_batch_round(ns, chunk, r, &s0, &cnt);
+        const int64_t ld = solve_batch_ld(cnt);
+        size_t in_doubles;
+        if (kind == 2) {
+            pack_soa(x0, 14, s0, cnt, ld, 0, hin.data());
+            pack_soa(x1, 14, s0, cnt, ld, 14, hin.data());
+            in_doubles = 28 * (size_t)ld;
+        } else { // sample-major, image 0's points then image 1's (the single-sample layout)
+            for (int64_t i = 0; i < cnt; ++i) {
+                std::memcpy(hin.data() + 2 * per * i, x0 + (s0 + i) * per, sizeof(double) * per);
+                std::memcpy(hin.data() + 2 * per * i + per, x1 + (s0 + i) * per, sizeof(double) * per);
+            }
+            in_doubles = 2 * (size_t)per * cnt;
+        }
+        MP_HIP(hipMemcpyAsync(d_in, hin.data(), sizeof(double) * in_doubles, hipMemcpyHostToDevice, X.stream));
+        MP_HIP(hipMemsetAsync(d_poses, 0, sizeof(Model) * 16 * cnt, X.stream));
+        if (kind == 0) {
+            MP_HIP(launch_sb_pt5(X.stream, d_in, (int)cnt, d_cand, d_ncand, d_poses, d_n));
+        } else if (kind == 1) {
+            // the estimator's root stage on the chunk's pseudo-pair, as debug_pt_roots runs it
+            pt_pseudo_pair(K, cnt, x0 + s0 * per, x1 + s0 * per, hpair, smp, list);
+            MP_HIP(hipMemcpyAsync(d_pair, hpair.data(), sizeof(double) * hpair.size(), hipMemcpyHostToDevice, X.stream));
+            MP_HIP(hipMemcpyAsync(d_smp, smp.data(), sizeof(int) * smp.size(), hipMemcpyHostToDevice, X.stream));
+            MP_HIP(hipMemcpyAsync(d_list, list.data(), sizeof(int) * list.size(), hipMemcpyHostToDevice, X.stream));
+            MP_HIP(hipMemsetAsync(d_cand, 0, sizeof(double) * kPtCandStride * (size_t)cnt, X.stream));
+            PairData D;
+            PairConst C;
+            pt_pseudo_views(kSF, K * cnt, d_pair, &D, &C);
+            MP_HIP(launch_pt_roots(X.stream, D, C, d_list, (int)cnt, d_smp, d_cand, d_ncand, d_pen));
+            MP_HIP(launch_sb_pt6_poses(X.stream, d_in, (int)cnt, d_cand, d_ncand, d_poses, d_n));
+        } else {
+            MP_HIP(launch_sb_pt7(X.stream, d_in, (int)ld, (int)cnt, d_F, d_poses, d_n));
+        }
+        MP_HIP(hipMemcpyAsync(poses + 16 * s0, d_poses, sizeof(Model) * 16 * cnt, hipMemcpyDeviceToHost, X.stream));
+        MP_HIP(hipMemcpyAsync(counts + s0, d_n, sizeof(int) * cnt, hipMemcpyDeviceToHost, X.stream));
+        MP_HIP(hipStreamSynchronize(X.stream)); // (the host staging is packed again for the next round)
+    }
 }
 
 void bougnoux_batch(int64_t k, const double *F, double *out, int device) {

@@ -106,6 +106,17 @@ int solve_point_direct(int kind, const double *x1, const double *x2, Model *pose
 void debug_pt_roots(int variant, int64_t ns, const double *pts0, const double *pts1, double *cand, int *ncand,
                     int device);
 
+// The standalone solvers over ns samples per call (mp_*_batch), in rounds of `chunk`
+// samples (0: the default, host/solve_batch_pack.h) on one set of device buffers kept by
+// the context.  Inputs sample-major, inside a sample the single-sample layout.
+// solve_md_batch: pose false -> sols (ns x 8 rows of width 4 / 5 / 6, alt 0 only), pose
+// true -> poses (ns x 8); relpose_batch: poses (ns x 16).  counts[s]: the sample's rows;
+// the slots past it are zero.  Each row is the single-sample entry's to the bit.
+void solve_md_batch(int variant, int alt, bool pose, int64_t ns, const double *x, const double *y, const double *dx,
+                    const double *dy, double *sols, Model *poses, int32_t *counts, int64_t chunk, int device);
+void relpose_batch(int kind, int64_t ns, const double *x0, const double *x1, Model *poses, int32_t *counts,
+                   int64_t chunk, int device);
+
 // estimate_scale_and_pose (src/solver.cpp:5-33) on the device; X, Y point-major n x 3
 void scale_and_pose_direct(const double *X, const double *Y, const double *W, int64_t n, Model *out, int device);
 // get_depths of num pairs on the device (see launch_get_depths); dims: num x 4

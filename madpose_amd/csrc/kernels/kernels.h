@@ -98,6 +98,23 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 hipError_t launch_point_direct_6pt(hipStream_t s, const double *in, const double *cand, const int *ncand,
                                    Model *poses, int *nposes);
 
+// The minimal solvers over many raw samples (solve_batch.h; mp_*_batch).  The outputs are
+// zeroed by the caller; a sample's rows past its count are not written.
+// MD solvers: in = the chunk as structure of arrays (host/solve_batch_pack.h pack_md_soa,
+// leading dimension ld); pose false: sols = ns x 8 rows of width 4 / 5 / 6 (alt 0 only),
+// pose true: poses = ns x 8 Models; counts = ns row counts.
+hipError_t launch_sb_md(hipStream_t s, int variant, int alt, bool pose, const double *in, int ld, int ns, double *sols,
+                        Model *poses, int *counts);
+// 5pt: in = ns x 30 doubles (unit bearings of image 0, then image 1); cand / ncand: the root
+// stage's workspace (kPtCandStride doubles and one int per sample); poses = ns x 16 Models
+hipError_t launch_sb_pt5(hipStream_t s, const double *in, int ns, double *cand, int *ncand, Model *poses, int *counts);
+// shared-focal 6pt poses from the root stage's output (launch_pt_roots on the chunk's
+// pseudo-pair); in = ns x 24 doubles (normalized 2-D points of image 0, then image 1)
+hipError_t launch_sb_pt6_poses(hipStream_t s, const double *in, int ns, const double *cand, const int *ncand,
+                               Model *poses, int *counts);
+// two-focal 7pt: in = 28 rows (structure of arrays, ld); Fws: 27 rows of workspace
+hipError_t launch_sb_pt7(hipStream_t s, const double *in, int ld, int ns, double *Fws, Model *poses, int *counts);
+
 // batched device LM: one workgroup per job; out[j] the refined model, status[j] 1
 // refined, 0 no residuals, 2 infeasible constant block (unchanged)
 hipError_t launch_lm_batch(hipStream_t s, const PairData &D, const PairConst &C, const LmJob *jobs, int njobs,

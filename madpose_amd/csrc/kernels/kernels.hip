@@ -1741,3 +1741,6 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 }
 
 } // namespace mp
+
+// the minimal solvers over many raw samples per launch (mp_*_batch)
+#include "solve_batch.h"
