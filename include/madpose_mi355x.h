@@ -215,6 +215,51 @@ int mp_debug_lm_refine_host(int variant, int64_t n, const double *x0, const doub
                             const int32_t *kinds, const int64_t *sample_offsets, const int32_t *sample_idx,
                             mp_model *models, int32_t *status);
 
+/* Device refinement of given poses over many pairs: for callers who have a pose already
+ * (a previous frame, a regressor, another estimator, an earlier run with other
+ * thresholds) and want it polished with the estimators' depth-aware cost.  The
+ * reference does this inside its estimator: LeastSquaresFit with
+ * use_all_solver_inliers (src/hybrid_ransac.h:406, 484-510) and the final least squares
+ * with its score < best rule (:186-203).  Per pair, with the current model m of score s,
+ * one round is:
+ *   1. the three squared-error arrays of m (is_for_inlier = true: the errors
+ *      mp_score_models returns);
+ *   2. list t = the ascending indices i with err[t][i] < threshold t (strict; the
+ *      thresholds after the estimators' option transform, for SF / TF in normalized units);
+ *   3. the LeastSquares call (kind 0) of mp_lm_refine_batch on the three lists from m,
+ *      with its size rule (status 3, model unchanged) and settings, on the device LM;
+ *   4. the score of the result as mp_score_models gives it;
+ *   5. status 1 and a strictly lower score: the model, its score and its lists are
+ *      accepted and the next round starts from them; otherwise the pair stops and keeps
+ *      what it had.
+ * At most `rounds` rounds run (1..64); the first round's step 1 also gives
+ * score_initial.  The reported lists and score are the accepted model's.  Models cross
+ * this boundary in user units as the estimators return them (SF / TF focals are divided
+ * by the pair's normalization scale on the way in and multiplied back on the way out;
+ * results[p].norm_scale is that scale); a pair without an accepted round keeps its
+ * model's bytes.  MP_SCALE_ONLY runs on the calibrated geometry as elsewhere.
+ * Pair layout exactly as mp_estimate_batch (offsets, min_depth 2 per pair, cameras 9 or 2
+ * per pair); inlier_idx (nullable): pair p at 3*offsets[p], list t at + t*n_p,
+ * results[p].num_inliers[t] entries.  A pair with n = 0 is legal: score 0, empty lists,
+ * status 3.  The pairs run in runs of `chunk` pairs whose data is resident on the device
+ * at once, one sweep launch and one LM launch per round over all pairs still running
+ * (chunk 0: as many pairs as hold MP_REFINE_RUN_CORRESPONDENCES correspondences, under
+ * 1 GiB of device memory).  num_pairs == 0 returns MP_OK without touching the device;
+ * negative counts, decreasing offsets, null required pointers, rounds outside 1..64,
+ * chunk < 0, a bad variant or invalid options give MP_EINVAL before any device call. */
+#define MP_REFINE_RUN_CORRESPONDENCES 4194304
+typedef struct mp_refine_result {
+    double score_initial, score_final, norm_scale;
+    int32_t rounds_run, rounds_accepted;
+    int32_t lm_status;      /* of the last round run: 0/1/2/3 as mp_lm_refine_batch; -1: no round ran */
+    int32_t num_inliers[3]; /* lists of the returned model */
+} mp_refine_result;
+int mp_refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                    const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                    const double *cam1, const mp_ransac_options *options, const mp_estimator_config *config,
+                    int32_t rounds, mp_model *models /* in/out, one per pair */, mp_refine_result *results,
+                    int32_t *inlier_idx /* nullable */, int64_t chunk, int device);
+
 /* bougnoux_focals (src/hybrid_pose_two_focal_estimator.cpp:11-32; numpy twin
  * madpose/utils.py:25-56 bougnoux_numpy with p1 = p2 = 0): squared focal lengths
  * (f0^2, f1^2) of k fundamental matrices F (k x 9, row-major) into out (k x 2), on

@@ -32,6 +32,8 @@ from .api import (  # noqa: F401
     profile_enable,
     profile_read,
     profile_reset,
+    RefineResult,
+    refine_batch,
     relpose_5pt,
     relpose_6pt_shared_focal,
     relpose_7pt_two_focal,

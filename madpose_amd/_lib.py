@@ -17,6 +17,8 @@ MP_OK, MP_EINVAL, MP_EDEVICE = 0, 1, 2
 CALIBRATED, SHARED_FOCAL, TWO_FOCAL, SCALE_ONLY = 0, 1, 2, 3
 # the batched solvers (mp_*_batch): samples per call, samples per round when chunk == 0
 SOLVE_BATCH_MAX, SOLVE_BATCH_CHUNK = 1 << 22, 32768
+# mp_refine_batch: correspondences per resident run when chunk == 0
+REFINE_RUN_CORRESPONDENCES = 1 << 22
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -118,7 +120,24 @@ class mp_kernel_profile(ctypes.Structure):
     ]
 
 
+class mp_refine_result(ctypes.Structure):
+    _fields_ = [
+        ("score_initial", ctypes.c_double),
+        ("score_final", ctypes.c_double),
+        ("norm_scale", ctypes.c_double),
+        ("rounds_run", ctypes.c_int32),
+        ("rounds_accepted", ctypes.c_int32),
+        ("lm_status", ctypes.c_int32),
+        ("num_inliers", ctypes.c_int32 * 3),
+    ]
+
+
 EXPORTS = {
+    "mp_refine_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
+                                       c_double_p, c_double_p, c_double_p, c_double_p,
+                                       ctypes.POINTER(mp_ransac_options), ctypes.POINTER(mp_estimator_config),
+                                       ctypes.c_int32, ctypes.POINTER(mp_model), ctypes.POINTER(mp_refine_result),
+                                       c_int32_p, ctypes.c_int64, ctypes.c_int]),
     "mp_estimate": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
                                    c_double_p, c_double_p, c_double_p, ctypes.POINTER(mp_ransac_options),
                                    ctypes.POINTER(mp_estimator_config), ctypes.POINTER(mp_model),

@@ -415,6 +415,98 @@ def estimate_batch(variant, pairs, options, est_config=None, device=None, num_st
     return out
 
 
+class RefineResult:
+    """One pair's outcome of refine_batch."""
+
+    def __init__(self):
+        self.model = None
+        self.score_initial = 0.0
+        self.score_final = 0.0
+        self.rounds_run = 0
+        self.rounds_accepted = 0
+        self.status = -1
+        self.inlier_indices = [np.zeros(0, dtype=np.int32) for _ in range(3)]
+        self.norm_scale = 1.0
+
+    def __repr__(self):
+        return (f"RefineResult(score {self.score_initial:.6g} -> {self.score_final:.6g}, rounds "
+                f"{self.rounds_accepted}/{self.rounds_run}, status={self.status}, "
+                f"inliers={[len(a) for a in self.inlier_indices]})")
+
+
+def refine_batch(variant, pairs, models, options, est_config=None, rounds=1, chunk=0, device=None):
+    """Refine given poses over many pairs on the device (mp_refine_batch).
+
+    pairs: estimate_batch's dicts; models: one pose object per pair, as the estimators
+    return them (user units).  Per pair and round: the inliers of the model under the
+    estimator's thresholds, the LeastSquares fit over all of them (device LM), and the
+    result kept when it scores strictly lower; a pair stops at its first round that is
+    not accepted (LeastSquaresFit with all inliers and the final least squares' rule,
+    src/hybrid_ransac.h:406, 484-510, 186-203).  All pairs of a run of `chunk` pairs (0:
+    a default bound on the run's correspondences) are resident at once, one sweep launch
+    and one LM launch per round.  Returns one RefineResult per pair: model, score_initial,
+    score_final, rounds_run, rounds_accepted, status (of the last LM: 1 refined, 0 no
+    residuals, 2 infeasible constant block, 3 too few inliers), inlier_indices (three
+    int32 arrays, the returned model's) and norm_scale."""
+    if len(models) != len(pairs):
+        raise ValueError(f"one model per pair: {len(models)} models for {len(pairs)} pairs")
+    if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL, L.SCALE_ONLY):
+        raise ValueError("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)")
+    if int(rounds) != rounds or not 1 <= rounds <= 64:
+        raise ValueError("rounds must be an integer in 1..64")
+    if int(chunk) != chunk or chunk < 0:
+        raise ValueError("chunk must be a non-negative integer (0: the default)")
+    if est_config is None:
+        est_config = EstimatorConfig()
+    o = options._to_c()
+    c = est_config._to_c()
+    P = len(pairs)
+    if P == 0:
+        return []
+    ncam = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
+    k0, k1 = ("K0", "K1") if ncam == 9 else ("pp0", "pp1")
+    x0s, x1s, d0s, d1s, mds, c0s, c1s, offs = [], [], [], [], [], [], [], [0]
+    for p in pairs:
+        x0 = _pts(p["x0"], "x0")
+        n = x0.shape[0]
+        x1 = _pts(p["x1"], "x1")
+        if x1.shape[0] != n:
+            raise ValueError("x0 and x1 must have the same number of rows")
+        x0s.append(x0.reshape(-1))
+        x1s.append(x1.reshape(-1))
+        d0s.append(_vec(p["depth0"], n, "depth0"))
+        d1s.append(_vec(p["depth1"], n, "depth1"))
+        mds.append(np.asarray(p.get("min_depth", (0.0, 0.0)), dtype=np.float64).reshape(2))
+        c0s.append(np.asarray(p[k0], dtype=np.float64).reshape(ncam))
+        c1s.append(np.asarray(p[k1], dtype=np.float64).reshape(ncam))
+        offs.append(offs[-1] + n)
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
+    X0, X1, D0, D1, MD, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, mds, c0s, c1s))
+    if offs[-1] == 0:  # (no correspondence at all: the arrays still need an address)
+        X0, X1, D0, D1 = np.zeros(2), np.zeros(2), np.zeros(1), np.zeros(1)
+    offsets = np.asarray(offs, dtype=np.int64)
+    arr = (L.mp_model * P)(*[_model_to_c(m, variant) for m in models])
+    res = (L.mp_refine_result * P)()
+    idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
+    L.check(L.lib().mp_refine_batch(variant, P, offsets.ctypes.data_as(L.c_int64_p), _dp(X0), _dp(X1), _dp(D0),
+                                    _dp(D1), _dp(MD), _dp(C0), _dp(C1), ctypes.byref(o), ctypes.byref(c),
+                                    int(rounds), arr, res, idx.ctypes.data_as(L.c_int32_p), int(chunk),
+                                    _DEFAULT_DEVICE if device is None else int(device)))
+    out = []
+    for p in range(P):
+        n = offs[p + 1] - offs[p]
+        r = RefineResult()
+        r.model = _model_from_c(arr[p], variant)
+        r.score_initial, r.score_final = float(res[p].score_initial), float(res[p].score_final)
+        r.rounds_run, r.rounds_accepted = int(res[p].rounds_run), int(res[p].rounds_accepted)
+        r.status = int(res[p].lm_status)
+        base = 3 * offs[p]
+        r.inlier_indices = [idx[base + t * n: base + t * n + res[p].num_inliers[t]].copy() for t in range(3)]
+        r.norm_scale = float(res[p].norm_scale)
+        out.append(r)
+    return out
+
+
 def lm_refine_batch(variant, x0, x1, depth0, depth1, min_depth, cam0, cam1, options, est_config, problems,
                     device=None, on_host=False):
     """Batched device LM (the LO's Ceres solves, src/optimizer.h:48-125 over
@@ -431,7 +523,7 @@ def lm_refine_batch(variant, x0, x1, depth0, depth1, min_depth, cam0, cam1, opti
     x1 = _pts(x1, "x1")
     d0, d1 = _vec(depth0, n, "depth0"), _vec(depth1, n, "depth1")
     md = np.asarray(min_depth, dtype=np.float64).reshape(2)
-    k = 9 if variant == L.CALIBRATED else 2
+    k = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
     c0 = np.ascontiguousarray(np.asarray(cam0, dtype=np.float64).reshape(k))
     c1 = np.ascontiguousarray(np.asarray(cam1, dtype=np.float64).reshape(k))
     P = len(problems)

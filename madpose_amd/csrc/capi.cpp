@@ -184,6 +184,22 @@ int mp_estimate_batch(int variant, int32_t num_pairs, const int64_t *offsets, co
     });
 }
 
+int mp_refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                    const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                    const double *cam1, const mp_ransac_options *options, const mp_estimator_config *config,
+                    int32_t rounds, mp_model *models, mp_refine_result *results, int32_t *inlier_idx, int64_t chunk,
+                    int device) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::Model) == sizeof(mp_model), "model layout");
+        static_assert(sizeof(mp::RefineResult) == sizeof(mp_refine_result), "refine result layout");
+        if (!options) throw std::invalid_argument("null options");
+        mp::refine_batch(variant, num_pairs, offsets, x0, x1, d0, d1, min_depth, cam0, cam1, to_opts(options),
+                         to_cfg(config), rounds, reinterpret_cast<mp::Model *>(models),
+                         reinterpret_cast<mp::RefineResult *>(results), inlier_idx, chunk, device);
+        return MP_OK;
+    });
+}
+
 int mp_get_depths(int dtype, int32_t num_pairs, const void *depth_maps, const int64_t *dims, const int64_t *pt_offsets,
                   const double *keypoints, void *out, int device) {
     return guarded([&]() {

@@ -47,6 +47,7 @@
 #include "batch_draw.h"
 #include "env.h"
 #include "lo_sweep.h"
+#include "refine_plan.h"
 #include "rng.h"
 #include "solve_batch_pack.h"
 
@@ -2474,6 +2475,263 @@ void lm_refine_batch_device(const PairInput &in, const RansacOptions &opts, cons
     for (size_t k = 0; k < which.size(); ++k) {
         models[which[k]] = out[k];
         status[which[k]] = st[k];
+    }
+}
+
+// Refinement of given models over many pairs (mp_refine_batch).  Per pair and round: the
+// inliers of the model (errors of launch_sweep below the thresholds), LeastSquares over
+// all of them on the device LM, and the result kept when it scores strictly lower
+// (LeastSquaresFit with use_all_solver_inliers and the final least squares' score <
+// best rule, src/hybrid_ransac.h:406, 484-510, 186-203).  The pairs of a run
+// (host/refine_plan.h) are resident at once; a round is one LM launch and one sweep
+// launch over the pairs still running, and the sweep that decides round r is the inlier
+// pass of round r + 1.  The host only drops stopped pairs from the launch lists.
+void refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                  const double *d0, const double *d1, const double *min_depth, const double *cam0, const double *cam1,
+                  const RansacOptions &opts, const EstimatorConfig &cfg, int rounds, Model *models,
+                  RefineResult *results, int32_t *inlier_idx, int64_t chunk, int device) {
+    if (variant < 0 || variant > 3)
+        throw std::invalid_argument("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)");
+    if (num_pairs < 0) throw std::invalid_argument("negative pair count");
+    if (rounds < 1 || rounds > 64) throw std::invalid_argument("rounds must be in 1..64");
+    if (chunk < 0) throw std::invalid_argument("chunk must not be negative");
+    {
+        PairInput none; // (the option checks of every entry point)
+        validate(none, opts);
+    }
+    if (num_pairs == 0) return;
+    if (!offsets || !min_depth || !cam0 || !cam1 || !models || !results)
+        throw std::invalid_argument("null offsets, min_depth, cameras, models or results");
+    if (offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+    for (int32_t p = 0; p < num_pairs; ++p) {
+        if (offsets[p + 1] < offsets[p]) throw std::invalid_argument("offsets must not decrease");
+        if (offsets[p + 1] - offsets[p] > kRefinePairMax) throw std::invalid_argument("pair too large");
+    }
+    if (offsets[num_pairs] > 0 && (!x0 || !x1 || !d0 || !d1)) throw std::invalid_argument("null input array");
+
+    const int nc = (variant == kCal || variant == kScaleOnly) ? 9 : 2;
+    const int v = variant == kScaleOnly ? kCal : variant;
+    const int kmd = v == kCal ? 3 : 4, kpt = v == kCal ? 5 : (v == kSF ? 6 : 7);
+    CtxLease lease(device);
+    hipStream_t stream = lease.c->stream;
+
+    for (const RefineRun &run : refine_plan(num_pairs, offsets, chunk)) {
+        const int np = run.p1 - run.p0;
+        const int64_t T = run.total;
+        // ---- problems, packed upload, pair records ----
+        std::vector<Problem> Ps(np);
+        std::vector<PairData> Dh(np);
+        std::vector<PairConst> Ch(np);
+        std::vector<int64_t> off(np), list_off(np);
+        std::vector<double> stage(6 * (size_t)T);
+        DevArray<double> d_data((size_t)kRefineRows * T);
+        DevArray<int> d_lists(6 * (size_t)T);
+        for (int k = 0; k < np; ++k) {
+            const int32_t p = run.p0 + k;
+            const int64_t o = offsets[p], n = offsets[p + 1] - o;
+            PairInput in;
+            in.variant = variant;
+            in.n = n;
+            in.x0 = x0 + 2 * o;
+            in.x1 = x1 + 2 * o;
+            in.d0 = d0 + o;
+            in.d1 = d1 + o;
+            in.min_depth[0] = min_depth[2 * p];
+            in.min_depth[1] = min_depth[2 * p + 1];
+            std::memcpy(in.cam0, cam0 + (size_t)nc * p, sizeof(double) * nc);
+            std::memcpy(in.cam1, cam1 + (size_t)nc * p, sizeof(double) * nc);
+            Problem &P = Ps[k];
+            P = make_problem(in, opts, cfg);
+            off[k] = o - offsets[run.p0];
+            list_off[k] = 3 * off[k];
+            refine_pack_pair(P.H.x0.data(), P.H.x1.data(), P.H.d0.data(), P.H.d1.data(), n, off[k], stage.data());
+            // (the host copies are not needed again: the LM runs on the device)
+            P.H.x0 = std::vector<double>();
+            P.H.x1 = std::vector<double>();
+            P.H.d0 = std::vector<double>();
+            P.H.d1 = std::vector<double>();
+            const double *rows[kRefineRows];
+            for (int r = 0; r < kRefineRows; ++r) rows[r] = d_data.p + refine_row(T, off[k], n, r);
+            PairData &D = Dh[k];
+            D.x0u = rows[0];
+            D.x0v = rows[1];
+            D.x1u = rows[2];
+            D.x1v = rows[3];
+            D.d0 = rows[4];
+            D.d1 = rows[5];
+            D.r0 = rows[6];
+            D.r1 = rows[7];
+            D.a0 = rows[8];
+            D.a1 = rows[9];
+            D.b0 = rows[10];
+            D.b1 = rows[11];
+            Ch[k] = P.C;
+        }
+        DevArray<PairData> d_D(np);
+        DevArray<PairConst> d_C(np);
+        DevArray<int64_t> d_list_off(np);
+        if (T > 0)
+            MP_HIP(hipMemcpyAsync(d_data.p, stage.data(), sizeof(double) * 6 * (size_t)T, hipMemcpyHostToDevice,
+                                  stream));
+        MP_HIP(hipMemcpyAsync(d_D.p, Dh.data(), sizeof(PairData) * np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_C.p, Ch.data(), sizeof(PairConst) * np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_list_off.p, list_off.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice, stream));
+        // pair preparation (the calibrated bearings and rays; the other variants read none)
+        if (v == kCal)
+            for (int k = 0; k < np; ++k) {
+                double *base = d_data.p;
+                const int64_t n = Ch[k].n;
+                auto row = [&](int r) { return base + refine_row(T, off[k], n, r); };
+                MP_HIP(launch_prep_pair(stream, Ch[k], Dh[k], row(6), row(7), row(8), row(9), row(10), row(11)));
+            }
+
+        // ---- per-pair state (models in problem units) ----
+        std::vector<Model> cur(np);
+        std::vector<double> score(np, 0.0);
+        std::vector<int> buf(np, 0);
+        for (int k = 0; k < np; ++k) {
+            const int32_t p = run.p0 + k;
+            cur[k] = models[p];
+            if (variant == kSF || variant == kTF) {
+                cur[k].focal0 /= Ps[k].norm_scale;
+                cur[k].focal1 /= Ps[k].norm_scale;
+            }
+            RefineResult &R = results[p];
+            std::memset(&R, 0, sizeof(R));
+            R.norm_scale = Ps[k].norm_scale;
+            R.lm_status = -1;
+        }
+        DevArray<RefineItem> d_items(np);
+        DevArray<ScoreRec> d_recs(np);
+        DevArray<RefineSweepOut> d_out(np);
+        DevArray<LmJob> d_jobs(np);
+        DevArray<LmPairRef> d_refs(np);
+        DevArray<Model> d_models(np);
+        DevArray<int> d_status(np);
+        std::vector<RefineItem> items;
+        std::vector<ScoreRec> recs;
+        std::vector<RefineSweepOut> outs;
+        // one sweep launch: model ms[j] of pair ks[j], lists into the buffer items[j].buf
+        auto sweep = [&](const std::vector<int> &ks, const std::vector<Model> &ms, bool other_buf) {
+            const size_t m = ks.size();
+            items.resize(m);
+            recs.resize(m);
+            outs.resize(m);
+            if (m == 0) return;
+            for (size_t j = 0; j < m; ++j) {
+                items[j].pair = ks[j];
+                items[j].buf = other_buf ? buf[ks[j]] ^ 1 : buf[ks[j]];
+                prepare_score_rec(Ch[ks[j]], ms[j], recs[j]);
+            }
+            MP_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(RefineItem) * m, hipMemcpyHostToDevice, stream));
+            MP_HIP(hipMemcpyAsync(d_recs.p, recs.data(), sizeof(ScoreRec) * m, hipMemcpyHostToDevice, stream));
+            MP_HIP(launch_refine_sweep(stream, v, d_D.p, d_C.p, d_items.p, d_recs.p, (int)m, d_list_off.p, d_lists.p,
+                                       3 * T, d_out.p));
+            MP_HIP(hipMemcpyAsync(outs.data(), d_out.p, sizeof(RefineSweepOut) * m, hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipStreamSynchronize(stream));
+        };
+
+        // ---- the initial sweep: score and lists of the given models ----
+        std::vector<int> running(np);
+        for (int k = 0; k < np; ++k) running[k] = k;
+        sweep(running, cur, false);
+        for (int k = 0; k < np; ++k) {
+            RefineResult &R = results[run.p0 + k];
+            score[k] = R.score_initial = R.score_final = outs[k].score;
+            for (int t = 0; t < 3; ++t) R.num_inliers[t] = outs[k].count[t];
+        }
+        // ---- rounds ----
+        std::vector<LmJob> jobs;
+        std::vector<LmPairRef> refs;
+        std::vector<int> which, st, cand_k;
+        std::vector<Model> lm_out, cand_m;
+        for (int round = 0; round < rounds && !running.empty(); ++round) {
+            jobs.clear();
+            refs.clear();
+            which.clear();
+            for (int k : running) {
+                RefineResult &R = results[run.p0 + k];
+                ++R.rounds_run;
+                const int *sz = R.num_inliers;
+                // too few data for the solver (the size test of least_squares): the pair stops
+                if ((sz[0] < kmd && sz[1] < kmd) || sz[2] < kpt) {
+                    R.lm_status = 3;
+                    continue;
+                }
+                LmJob J = make_lm_job(Ps[k], cfg, sz, 0, false, cur[k]);
+                // (the lists of a pair lie n apart, not back to back)
+                J.off1 = Ch[k].n;
+                J.off2 = 2 * Ch[k].n;
+                jobs.push_back(J);
+                LmPairRef ref;
+                ref.pair = k;
+                ref.pad = 0;
+                ref.idx_off = refine_list(T, off[k], Ch[k].n, buf[k], 0);
+                refs.push_back(ref);
+                which.push_back(k);
+            }
+            running.clear();
+            if (jobs.empty()) break;
+            const size_t nj = jobs.size();
+            lm_out.resize(nj);
+            st.resize(nj);
+            MP_HIP(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(LmJob) * nj, hipMemcpyHostToDevice, stream));
+            MP_HIP(hipMemcpyAsync(d_refs.p, refs.data(), sizeof(LmPairRef) * nj, hipMemcpyHostToDevice, stream));
+            MP_HIP(launch_lm_pairs(stream, v, d_D.p, d_C.p, d_jobs.p, d_refs.p, (int)nj, d_lists.p, d_models.p,
+                                   d_status.p));
+            MP_HIP(hipMemcpyAsync(lm_out.data(), d_models.p, sizeof(Model) * nj, hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipMemcpyAsync(st.data(), d_status.p, sizeof(int) * nj, hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipStreamSynchronize(stream));
+            cand_k.clear();
+            cand_m.clear();
+            for (size_t j = 0; j < nj; ++j) {
+                results[run.p0 + which[j]].lm_status = st[j];
+                if (st[j] != 1) continue; // (model unchanged: the pair stops)
+                cand_k.push_back(which[j]);
+                cand_m.push_back(lm_out[j]);
+            }
+            // the candidates' scores and lists, into each pair's other list buffer
+            sweep(cand_k, cand_m, true);
+            for (size_t j = 0; j < cand_k.size(); ++j) {
+                const int k = cand_k[j];
+                if (!(outs[j].score < score[k])) continue; // (not strictly lower: the pair stops)
+                RefineResult &R = results[run.p0 + k];
+                cur[k] = cand_m[j];
+                score[k] = R.score_final = outs[j].score;
+                for (int t = 0; t < 3; ++t) R.num_inliers[t] = outs[j].count[t];
+                buf[k] ^= 1;
+                ++R.rounds_accepted;
+                running.push_back(k);
+            }
+        }
+        // ---- results: models back in user units, the accepted models' lists ----
+        for (int k = 0; k < np; ++k) {
+            const int32_t p = run.p0 + k;
+            if (results[p].rounds_accepted == 0) continue; // (the given model, untouched)
+            Model m = cur[k];
+            if (variant == kSF) {
+                m.focal0 *= Ps[k].norm_scale;
+                m.focal1 = m.focal0;
+            } else if (variant == kTF) {
+                m.focal0 *= Ps[k].norm_scale;
+                m.focal1 *= Ps[k].norm_scale;
+            }
+            models[p] = m;
+        }
+        if (inlier_idx && T > 0) {
+            const bool both = std::any_of(buf.begin(), buf.end(), [](int b) { return b != 0; });
+            std::vector<int> lists((both ? 6 : 3) * (size_t)T);
+            MP_HIP(hipMemcpyAsync(lists.data(), d_lists.p, sizeof(int) * lists.size(), hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipStreamSynchronize(stream));
+            for (int k = 0; k < np; ++k) {
+                const int32_t p = run.p0 + k;
+                const int64_t n = Ch[k].n;
+                for (int t = 0; t < 3; ++t)
+                    std::memcpy(inlier_idx + 3 * offsets[p] + t * n, lists.data() + refine_list(T, off[k], n, buf[k], t),
+                                sizeof(int) * (size_t)results[p].num_inliers[t]);
+            }
+        }
+        MP_HIP(hipStreamSynchronize(stream));
     }
 }
 

@@ -93,6 +93,26 @@ void lm_refine_batch_host(const PairInput &in, const RansacOptions &opts, const 
                           const int32_t *kinds, const int64_t *offsets, const int32_t *idx, Model *models,
                           int32_t *status);
 
+// Device refinement of given models over many pairs (mp_refine_batch).  Pairs laid out
+// as mp_estimate_batch's (offsets, 2 min depths and 9 / 2 camera values per pair); models:
+// one per pair, in and out, user units.  Per pair and round: the inlier lists of the model
+// (launch_sweep's errors below PairConst::thr), LeastSquares (kind 0 of
+// lm_refine_batch_device) over them, the result accepted when the LM status is 1 and its
+// score (score_models') is strictly lower; a pair stops at its first round without an
+// accepted model, or after `rounds`.  A pair no round of which was accepted keeps its
+// model's bytes.  Pairs run in resident runs of `chunk` pairs (0: host/refine_plan.h's
+// default bound on a run's correspondences).  inlier_idx (nullable): as mp_estimate_batch.
+struct RefineResult {
+    double score_initial, score_final, norm_scale;
+    int32_t rounds_run, rounds_accepted;
+    int32_t lm_status; // of the last round run (0..3 as lm_refine_batch_device), -1: none ran
+    int32_t num_inliers[3];
+};
+void refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                  const double *d0, const double *d1, const double *min_depth, const double *cam0, const double *cam1,
+                  const RansacOptions &opts, const EstimatorConfig &cfg, int rounds, Model *models,
+                  RefineResult *results, int32_t *inlier_idx, int64_t chunk, int device);
+
 // Standalone solvers on the device (mp_solve_* / mp_relpose_5pt).
 // alt: 0 default MD solver, 1 use_ours, 2 use_4p4d (two-focal)
 int solve_md_direct(int variant, const double *x, const double *y, const double *dx, const double *dy, double *sols,

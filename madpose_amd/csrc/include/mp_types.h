@@ -121,6 +121,25 @@ struct LmJob {
     Model m;
 };
 
+// Many resident pairs per launch (kernels/refine_batch.h, lm_pairs_kernel): the pairs'
+// PairData / PairConst records sit in device arrays and a work item names its pair.
+// LmPairRef: beside LmJob j, the pair of the job and where its block lists start (ints
+// from the launch's idx; LmJob's offsets count from there).
+struct LmPairRef {
+    int pair, pad;
+    int64_t idx_off;
+};
+// One sweep of refine_sweep_kernel: the pair, and which of the two list buffers the
+// inlier lists go to.
+struct RefineItem {
+    int pair, buf;
+};
+// Its outcome: the MSAC score (score_models_kernel's sum) and the three list lengths.
+struct RefineSweepOut {
+    double score;
+    int count[3], pad;
+};
+
 constexpr int kMaxModelsCal = 10; // MD <= 4, 5pt <= 10
 constexpr int kMaxModelsSF = 16;  // MD <= 8, 6pt <= 15
 constexpr int kMaxModelsTF = 4;   // MD <= 4, 7pt <= 3

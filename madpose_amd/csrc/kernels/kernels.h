@@ -120,6 +120,19 @@ hipError_t launch_sb_pt7(hipStream_t s, const double *in, int ld, int ns, double
 hipError_t launch_lm_batch(hipStream_t s, const PairData &D, const PairConst &C, const LmJob *jobs, int njobs,
                            const int *idx, Model *out, int *status);
 
+// Many resident pairs per launch (refine_batch.h; mp_refine_batch).  Ds / Cs: one record
+// per pair in device memory; variant: the pairs' common PairConst::variant.
+// Sweep of item k = (pair, list buffer) with model record recs[k]: out[k] = the score as
+// launch_score_models gives it and the lengths of the three ascending inlier lists (err <
+// thr, errors as launch_sweep's), written to lists + buf * buf_stride + list_off[pair] +
+// t * n.  One workgroup per item.
+hipError_t launch_refine_sweep(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                               const RefineItem *items, const ScoreRec *recs, int nitems, const int64_t *list_off,
+                               int *lists, int64_t buf_stride, RefineSweepOut *out);
+// launch_lm_batch with job j on pair refs[j].pair, its block lists at idx + refs[j].idx_off
+hipError_t launch_lm_pairs(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs, const LmJob *jobs,
+                           const LmPairRef *refs, int njobs, const int *idx, Model *out, int *status);
+
 // squared Bougnoux focals of k fundamental matrices (9 doubles each) into out (2 each)
 hipError_t launch_bougnoux(hipStream_t s, const double *F, int64_t k, double *out);
 

@@ -1744,3 +1744,5 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 
 // the minimal solvers over many raw samples per launch (mp_*_batch)
 #include "solve_batch.h"
+// refinement of given models over many resident pairs (mp_refine_batch)
+#include "refine_batch.h"

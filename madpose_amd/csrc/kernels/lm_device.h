@@ -567,219 +567,30 @@ __device__ inline double lm_amb_norm2(const LmParams &p) {
 }
 
 // One workgroup per job: out[job] = the refined model, status[job] = 1 (refined),
-// 0 (no residuals: unchanged), 2 (a constant bounded block starts infeasible: unchanged)
+// 0 (no residuals: unchanged), 2 (a constant bounded block starts infeasible: unchanged).
+// Every job on the one pair given by value.  (The body: lm_problem.inc.)
 template <int V>
 __global__ void __launch_bounds__(kLmBlock) lm_batch_kernel(PairData D, PairConst C, const LmJob *jobs,
                                                            const int *idx, Model *out, int *status) {
-    constexpr int NA = V == kCal ? kLF0 : (V == kSF ? kLF0 + 1 : kLNFull);
-    constexpr int kPack = LmShared<NA>::kPack;
-    __shared__ LmShared<NA> sh;
-    const LmJob &J = jobs[blockIdx.x]; // (read in place: uniform, kept out of registers)
-    const bool t0 = threadIdx.x == 0;
-    // ---- setup (lm_refine in host/lm.cpp) ----
-    if (t0) {
-        const bool has_o0 = J.n0 > 0, has_s_o1 = J.n1 > 0;
-        for (int k = 0; k < kLNFull; ++k) {
-            sh.col[k] = -1;
-            sh.has_lo[k] = 0;
-            sh.lo[k] = 0.0;
-        }
-        for (int k = 0; k < 6; ++k) sh.col[k] = k;
-        if (has_s_o1) {
-            sh.col[kLS] = kLS;
-            sh.has_lo[kLS] = 1;
-            sh.lo[kLS] = 1e-2;
-        }
-        if (has_o0 && J.use_shift) sh.col[kLO0] = kLO0;
-        if (has_s_o1 && J.use_shift) sh.col[kLO1] = kLO1;
-        if (J.min_depth_constraint) {
-            sh.has_lo[kLO0] = sh.has_lo[kLO1] = 1;
-            sh.lo[kLO0] = -C.min_depth[0] + 1e-2;
-            sh.lo[kLO1] = -C.min_depth[1] + 1e-2;
-        }
-        if (V == kSF) sh.col[kLF0] = kLF0;
-        if (V == kTF) {
-            sh.col[kLF0] = kLF0;
-            sh.col[kLF1] = kLF1;
-            sh.has_lo[kLF0] = sh.has_lo[kLF1] = 1;
-            sh.lo[kLF0] = sh.lo[kLF1] = 1e-6;
-        }
-        LmParams &x = sh.x;
-        lm_rot_to_quat(J.m.R, x.q);
-        lm_quat_to_rot(x.q, x.R);
-        for (int k = 0; k < 3; ++k) x.t[k] = J.m.t[k];
-        x.s = J.m.scale;
-        x.o0 = J.m.offset0;
-        x.o1 = J.m.offset1;
-        x.f0 = J.m.focal0;
-        x.f1 = J.m.focal1;
-        sh.best = x;
-        sh.cur = 0;
-        sh.action = 1;
-        if (J.n0 + J.n1 + J.n2 == 0) sh.action = 0;
-        // constant bounded blocks must start feasible (Ceres Program::IsFeasible)
-        if (!J.use_shift && J.min_depth_constraint) {
-            if (has_o0 && x.o0 < sh.lo[kLO0]) sh.action = 0;
-            if (has_s_o1 && x.o1 < sh.lo[kLO1]) sh.action = 0;
-        }
-        if (J.n0 + J.n1 + J.n2 == 0)
-            status[blockIdx.x] = 0;
-        else
-            status[blockIdx.x] = sh.action ? 1 : 2;
-    }
-    __syncthreads();
-    if (sh.action == 0) {
-        if (t0) out[blockIdx.x] = J.m;
-        return;
-    }
-    bool act[NA];
-#pragma unroll
-    for (int a = 0; a < NA; ++a) act[a] = sh.col[a] >= 0;
-    lm_evaluate<V, NA>(D, C, J, idx, sh.x, sh, sh.red[0]);
-    // ---- trust-region loop (lane 0 decides, every lane evaluates) ----
-    double radius = 1e4, decrease = 2.0;
-    const int max_nonmono = J.nonmonotonic ? 5 : 0;
-    double ref_cost = 0, min_cost = 0, cand_ref = 0, acc_ref = 0.0, acc_cand = 0.0;
-    int n_nonmono = 0, iter = 0;
-    if (t0) {
-        ref_cost = min_cost = cand_ref = sh.red[0][kPack + NA];
-        sh.action = (lm_gmax<NA>(sh.red[0], act) <= J.gtol) ? 0 : 2;
-    }
-    __syncthreads();
-    while (sh.action != 0) {
-        if (t0) {
-            // propose a step from x (repeated while the damped system is not positive definite)
-            const double *R = sh.red[sh.cur];
-            int prop = 0;
-            while (iter < J.max_iter) {
-                ++iter;
-                double d[NA];
-                if (!lm_step<NA>(R, act, radius, d)) {
-                    radius /= decrease;
-                    decrease *= 2.0;
-                    if (radius < 1e-32) break;
-                    continue;
-                }
-#pragma unroll
-                for (int a = 0; a < NA; ++a) sh.d[a] = d[a];
-                // candidate = Plus(x, d), projected onto the bounds
-                const LmParams &x = sh.x;
-                LmParams c = x;
-                {
-                    const double nd = sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-                    if (nd > 0) {
-                        const double sn = sin(nd) / nd;
-                        const double qd[4] = {cos(nd), sn * d[0], sn * d[1], sn * d[2]};
-                        const double *q = x.q;
-                        c.q[0] = qd[0] * q[0] - qd[1] * q[1] - qd[2] * q[2] - qd[3] * q[3];
-                        c.q[1] = qd[0] * q[1] + qd[1] * q[0] + qd[2] * q[3] - qd[3] * q[2];
-                        c.q[2] = qd[0] * q[2] - qd[1] * q[3] + qd[2] * q[0] + qd[3] * q[1];
-                        c.q[3] = qd[0] * q[3] + qd[1] * q[2] - qd[2] * q[1] + qd[3] * q[0];
-                    }
-#pragma unroll
-                    for (int k = 0; k < 3; ++k) c.t[k] = x.t[k] + d[3 + k];
-                    auto upd = [&](int slot, double v, double dv) {
-                        if (sh.col[slot] < 0) return v;
-                        v += dv;
-                        return (sh.has_lo[slot] && v < sh.lo[slot]) ? sh.lo[slot] : v;
-                    };
-                    c.s = upd(kLS, c.s, d[kLS]);
-                    c.o0 = upd(kLO0, c.o0, d[kLO0]);
-                    c.o1 = upd(kLO1, c.o1, d[kLO1]);
-                    if (NA > kLF0) c.f0 = upd(kLF0, c.f0, d[NA > kLF0 ? kLF0 : 0]);
-                    if (NA > kLF1) c.f1 = upd(kLF1, c.f1, d[NA > kLF1 ? kLF1 : 0]);
-                    lm_quat_to_rot(c.q, c.R);
-                }
-                double step2 = 0;
-                {
-                    const double dd[12] = {c.q[0] - x.q[0], c.q[1] - x.q[1], c.q[2] - x.q[2], c.q[3] - x.q[3],
-                                           c.t[0] - x.t[0], c.t[1] - x.t[1], c.t[2] - x.t[2], c.s - x.s,
-                                           c.o0 - x.o0,     c.o1 - x.o1,     c.f0 - x.f0,     c.f1 - x.f1};
-#pragma unroll
-                    for (int k = 0; k < 12; ++k) step2 += dd[k] * dd[k];
-                }
-                if (sqrt(step2) <= J.ptol * (sqrt(lm_amb_norm2(x)) + J.ptol)) break; // parameter tolerance
-                sh.c = c;
-                prop = 1;
-                break;
-            }
-            sh.prop = prop;
-        }
-        __syncthreads();
-        if (sh.prop == 0) break;
-        lm_evaluate<V, NA>(D, C, J, idx, sh.c, sh, sh.red[sh.cur ^ 1]);
-        if (t0) {
-            const double *R = sh.red[sh.cur], *Rc = sh.red[sh.cur ^ 1];
-            const double cost = R[kPack + NA], cand_cost = Rc[kPack + NA];
-            sh.action = 2;
-            if (fabs(cost - cand_cost) <= J.ftol * cost) {
-                sh.action = 0; // function tolerance
-            } else {
-                double d[NA];
-#pragma unroll
-                for (int a = 0; a < NA; ++a) d[a] = sh.d[a];
-                double gd = 0, jd2 = 0;
-#pragma unroll
-                for (int a = 0; a < NA; ++a) {
-                    gd += (act[a] ? R[kPack + a] : 0.0) * d[a];
-#pragma unroll
-                    for (int b2 = 0; b2 < NA; ++b2) {
-                        const double h = (act[a] && act[b2]) ? R[a <= b2 ? lm_up(a, b2, NA) : lm_up(b2, a, NA)] : 0.0;
-                        jd2 += d[a] * h * d[b2];
-                    }
-                }
-                const double mcc = -(gd + 0.5 * jd2);
-                const double rho = (mcc > 0 && isfinite(cand_cost))
-                                       ? fmax((cost - cand_cost) / mcc, (ref_cost - cand_cost) / (acc_ref + mcc))
-                                       : -1.0;
-                if (rho > 1e-3) {
-                    sh.x = sh.c;
-                    sh.cur ^= 1;
-                    // Ceres TrustRegionStepEvaluator::StepAccepted
-                    acc_cand += mcc;
-                    acc_ref += mcc;
-                    if (cand_cost < min_cost) {
-                        min_cost = cand_cost;
-                        n_nonmono = 0;
-                        cand_ref = cand_cost;
-                        acc_cand = 0.0;
-                        sh.best = sh.x;
-                    } else {
-                        ++n_nonmono;
-                        if (cand_cost > cand_ref) {
-                            cand_ref = cand_cost;
-                            acc_cand = 0.0;
-                        }
-                    }
-                    if (n_nonmono == max_nonmono) {
-                        ref_cost = cand_ref;
-                        acc_ref = acc_cand;
-                    }
-                    radius = fmin(1e16, radius / fmax(1.0 / 3.0, 1.0 - pow(2.0 * rho - 1.0, 3.0)));
-                    decrease = 2.0;
-                    if (lm_gmax<NA>(Rc, act) <= J.gtol) sh.action = 0;
-                } else {
-                    radius /= decrease;
-                    decrease *= 2.0;
-                    if (radius < 1e-32) sh.action = 0;
-                }
-            }
-            if (iter >= J.max_iter) sh.action = 0;
-        }
-        __syncthreads();
-    }
-    if (t0) {
-        Model m = J.m;
-        const LmParams &b = sh.best;
-        lm_quat_to_rot(b.q, m.R);
-        for (int k = 0; k < 3; ++k) m.t[k] = b.t[k];
-        m.scale = b.s;
-        m.offset0 = b.o0;
-        m.offset1 = b.o1;
-        m.focal0 = b.f0;
-        m.focal1 = (V == kSF) ? b.f0 : b.f1;
-        out[blockIdx.x] = m;
-    }
+#include "lm_problem.inc"
+}
+
+// The same over many resident pairs: job j works on pair refs[j].pair (Ds / Cs: one
+// record per pair in device memory) with its block lists at idx + refs[j].idx_off (LmJob's
+// offsets count from there).  restrict: the pair records are read through the scalar
+// cache like the by-value arguments of lm_batch_kernel (the stores to out / status could
+// alias them otherwise); flatten: lm_evaluate inlined here too (as a call it ran through
+// the stack, 650-950 bytes of scratch per lane).
+template <int V>
+__global__ void __launch_bounds__(kLmBlock) __attribute__((flatten))
+    lm_pairs_kernel(const PairData *__restrict__ Ds, const PairConst *__restrict__ Cs, const LmJob *__restrict__ jobs,
+                    const LmPairRef *__restrict__ refs, const int *__restrict__ idx_all, Model *__restrict__ out,
+                    int *__restrict__ status) {
+    const LmPairRef ref = refs[blockIdx.x];
+    const PairData &D = Ds[ref.pair];
+    const PairConst &C = Cs[ref.pair];
+    const int *idx = idx_all + ref.idx_off;
+#include "lm_problem.inc"
 }
 
 } // namespace
