@@ -260,6 +260,63 @@ int mp_refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, cons
                     int32_t rounds, mp_model *models /* in/out, one per pair */, mp_refine_result *results,
                     int32_t *inlier_idx /* nullable */, int64_t chunk, int device);
 
+/* Ranking of candidate poses over many pairs on the device: for callers who have several
+ * poses per pair (from several depth models, a retrieval or localisation prior beside an
+ * estimator, runs with other thresholds, the batched solvers) and need the one the
+ * estimators' depth-aware MSAC cost prefers, with the correspondences it explains.  Pair
+ * p has n_p correspondences and the candidates models[model_offsets[p] ..
+ * model_offsets[p+1]), in user units as the estimators return them and as mp_refine_batch
+ * takes them (SF / TF focals are divided once by the pair's normalization scale,
+ * results[p].norm_scale, on the way in; MP_SCALE_ONLY runs on the calibrated geometry as
+ * elsewhere).  For every candidate m (its index into models):
+ *   1. scores[m] = the score mp_score_models returns for the same pair, options, config
+ *      and the model in problem units, bit for bit;
+ *   2. counts[3m + t], t = 0..2, = the number of i with err[t][i] < threshold t (strict;
+ *      the is_for_inlier = true errors mp_score_models returns, the thresholds after the
+ *      estimators' option transform): the length of the list mp_refine_batch would form.
+ * Per pair:
+ *   1. best_index by the reference's GetBestEstimatedModelId (src/hybrid_ransac.h:245-263):
+ *      start at DBL_MAX, walk the candidates in order, take one only on a strict <.  Of
+ *      equal scores the first wins; a NaN or infinite score never wins.  With no
+ *      candidates, or none that wins: best_index -1, best_score DBL_MAX, counts 0, empty
+ *      lists;
+ *   2. the winner's three ascending inlier lists (rule 2 above) in mp_refine_batch's
+ *      inlier_idx layout; they and best_score equal the lists and score_initial that
+ *      mp_refine_batch reports for that model.
+ * A pair with n = 0 is legal: every score is 0, so candidate 0 wins if there is one.  No
+ * min_depth is taken: no score depends on it.  Pair layout, `chunk` and its default run
+ * bound as mp_refine_batch.  model_chunk: the candidates whose score records are on the
+ * device at once (0: MP_SELECT_SLAB_MODELS); a slab may cut through a pair's candidates.
+ * Results depend on neither chunk nor model_chunk.  scores, counts and inlier_idx are
+ * nullable.  num_pairs == 0 returns MP_OK without touching the device; negative counts,
+ * decreasing or negative offsets or model_offsets, more than 2^28 candidates, null
+ * required pointers (models too when there is a candidate), chunk < 0, model_chunk < 0, a
+ * bad variant or invalid options give MP_EINVAL before any device call. */
+#define MP_SELECT_SLAB_MODELS 65536
+#define MP_SELECT_TILE 1 /* candidates per device work item */
+typedef struct mp_select_result {
+    double best_score, norm_scale;
+    int32_t best_index;     /* within the pair's candidates; -1: none */
+    int32_t num_inliers[3]; /* the winner's lists */
+} mp_select_result;         /* 32 bytes */
+int mp_select_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                    const double *d0, const double *d1, const double *cam0, const double *cam1,
+                    const mp_ransac_options *options, const mp_estimator_config *config,
+                    const int64_t *model_offsets, const mp_model *models,
+                    double *scores /* nullable: one per candidate */, int32_t *counts /* nullable: 3 per candidate */,
+                    mp_select_result *results, int32_t *inlier_idx /* nullable */, int64_t chunk,
+                    int64_t model_chunk, int device);
+/* Measurement hooks of mp_select_batch (tools/select_batch_bench.py).
+ * mp_debug_select_tile: candidates per work item of the following calls (1, 2, 4 or 8; 0:
+ * MP_SELECT_TILE); returns the previous setting, -1 for a bad value.  Only MP_SELECT_TILE
+ * is pinned to mp_score_models' bits; another size may move a score in its last bits.
+ * mp_debug_select_timing: six stage times in ms of the last call made
+ * while profiling was enabled (mp_profile_enable) -- pair setup, host record preparation,
+ * record upload, select_score, select_argmin with its copies back, the winners' sweep
+ * with its copies back; every stage is waited for then, so nothing overlaps. */
+int mp_debug_select_tile(int tile);
+int mp_debug_select_timing(double *out_ms /* 6 */);
+
 /* bougnoux_focals (src/hybrid_pose_two_focal_estimator.cpp:11-32; numpy twin
  * madpose/utils.py:25-56 bougnoux_numpy with p1 = p2 = 0): squared focal lengths
  * (f0^2, f1^2) of k fundamental matrices F (k x 9, row-major) into out (k x 2), on

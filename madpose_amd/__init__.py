@@ -39,6 +39,8 @@ from .api import (  # noqa: F401
     relpose_7pt_two_focal,
     relpose_batch,
     score_models,
+    SelectResult,
+    select_batch,
     set_device,
     solve_scale_and_shift,
     solve_scale_and_shift_batch,

@@ -19,6 +19,9 @@ CALIBRATED, SHARED_FOCAL, TWO_FOCAL, SCALE_ONLY = 0, 1, 2, 3
 SOLVE_BATCH_MAX, SOLVE_BATCH_CHUNK = 1 << 22, 32768
 # mp_refine_batch: correspondences per resident run when chunk == 0
 REFINE_RUN_CORRESPONDENCES = 1 << 22
+# mp_select_batch: candidates per record slab when model_chunk == 0; candidates per device
+# work item (MP_SELECT_SLAB_MODELS, MP_SELECT_TILE)
+SELECT_SLAB_MODELS, SELECT_TILE = 1 << 16, 1
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -132,7 +135,23 @@ class mp_refine_result(ctypes.Structure):
     ]
 
 
+class mp_select_result(ctypes.Structure):
+    _fields_ = [
+        ("best_score", ctypes.c_double),
+        ("norm_scale", ctypes.c_double),
+        ("best_index", ctypes.c_int32),
+        ("num_inliers", ctypes.c_int32 * 3),
+    ]
+
+
 EXPORTS = {
+    "mp_select_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
+                                       c_double_p, c_double_p, c_double_p, ctypes.POINTER(mp_ransac_options),
+                                       ctypes.POINTER(mp_estimator_config), c_int64_p, ctypes.POINTER(mp_model),
+                                       c_double_p, c_int32_p, ctypes.POINTER(mp_select_result), c_int32_p,
+                                       ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "mp_debug_select_tile": (ctypes.c_int, [ctypes.c_int]),
+    "mp_debug_select_timing": (ctypes.c_int, [c_double_p]),
     "mp_refine_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
                                        c_double_p, c_double_p, c_double_p, c_double_p,
                                        ctypes.POINTER(mp_ransac_options), ctypes.POINTER(mp_estimator_config),

@@ -507,6 +507,107 @@ def refine_batch(variant, pairs, models, options, est_config=None, rounds=1, chu
     return out
 
 
+class SelectResult:
+    """One pair's outcome of select_batch."""
+
+    def __init__(self):
+        self.index = -1
+        self.model = None
+        self.score = float(np.finfo(np.float64).max)
+        self.inlier_indices = [np.zeros(0, dtype=np.int32) for _ in range(3)]
+        self.norm_scale = 1.0
+        self.scores = None
+        self.counts = None
+
+    def __repr__(self):
+        return (f"SelectResult(index={self.index}, score={self.score:.6g}, "
+                f"inliers={[len(a) for a in self.inlier_indices]})")
+
+
+def select_batch(variant, pairs, candidates, options, est_config=None, with_scores=False, with_counts=False,
+                 chunk=0, model_chunk=0, device=None):
+    """Rank candidate poses over many pairs on the device (mp_select_batch).
+
+    pairs: estimate_batch's dicts; candidates: one sequence of pose objects per pair, as
+    the estimators return them (user units); a sequence may be empty.  Every candidate gets
+    the estimators' MSAC score (score_models' value for it, bit for bit) and the three
+    counts of errors below the thresholds; per pair the first candidate with the lowest
+    score wins (the reference's GetBestEstimatedModelId: strict <, a NaN or infinite score
+    never wins).  All pairs of a run of `chunk` pairs (0: refine_batch's default bound) are
+    resident at once; the score records of `model_chunk` candidates (0: the default) are on
+    the device at a time; results depend on neither.  Returns one SelectResult per pair:
+    index (-1: no winner), model (the chosen candidate object itself, or None), score
+    (DBL_MAX without a winner), inlier_indices (three int32 arrays, the winner's, as
+    refine_batch would form them), norm_scale, scores (float64, one per candidate, with
+    with_scores, else None) and counts (int32 K x 3, with with_counts, else None)."""
+    if len(candidates) != len(pairs):
+        raise ValueError(f"one candidate list per pair: {len(candidates)} lists for {len(pairs)} pairs")
+    if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL, L.SCALE_ONLY):
+        raise ValueError("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)")
+    for name, val in (("chunk", chunk), ("model_chunk", model_chunk)):
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer, float)) or int(val) != val or val < 0:
+            raise ValueError(f"{name} must be a non-negative integer (0: the default)")
+    if est_config is None:
+        est_config = EstimatorConfig()
+    o = options._to_c()
+    c = est_config._to_c()
+    P = len(pairs)
+    if P == 0:
+        return []
+    ncam = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
+    k0, k1 = ("K0", "K1") if ncam == 9 else ("pp0", "pp1")
+    x0s, x1s, d0s, d1s, c0s, c1s, offs, moffs = [], [], [], [], [], [], [0], [0]
+    for p, cands in zip(pairs, candidates):
+        x0 = _pts(p["x0"], "x0")
+        n = x0.shape[0]
+        x1 = _pts(p["x1"], "x1")
+        if x1.shape[0] != n:
+            raise ValueError("x0 and x1 must have the same number of rows")
+        x0s.append(x0.reshape(-1))
+        x1s.append(x1.reshape(-1))
+        d0s.append(_vec(p["depth0"], n, "depth0"))
+        d1s.append(_vec(p["depth1"], n, "depth1"))
+        c0s.append(np.asarray(p[k0], dtype=np.float64).reshape(ncam))
+        c1s.append(np.asarray(p[k1], dtype=np.float64).reshape(ncam))
+        offs.append(offs[-1] + n)
+        moffs.append(moffs[-1] + len(cands))
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
+    X0, X1, D0, D1, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, c0s, c1s))
+    if offs[-1] == 0:  # (no correspondence at all: the arrays still need an address)
+        X0, X1, D0, D1 = np.zeros(2), np.zeros(2), np.zeros(1), np.zeros(1)
+    offsets = np.asarray(offs, dtype=np.int64)
+    model_offsets = np.asarray(moffs, dtype=np.int64)
+    M = moffs[-1]
+    arr = (L.mp_model * max(M, 1))(*[_model_to_c(m, variant) for cands in candidates for m in cands])
+    res = (L.mp_select_result * P)()
+    idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
+    scores = np.zeros(max(M, 1), dtype=np.float64) if with_scores else None
+    counts = np.zeros(3 * max(M, 1), dtype=np.int32) if with_counts else None
+    L.check(L.lib().mp_select_batch(variant, P, offsets.ctypes.data_as(L.c_int64_p), _dp(X0), _dp(X1), _dp(D0),
+                                    _dp(D1), _dp(C0), _dp(C1), ctypes.byref(o), ctypes.byref(c),
+                                    model_offsets.ctypes.data_as(L.c_int64_p), arr,
+                                    None if scores is None else _dp(scores),
+                                    None if counts is None else counts.ctypes.data_as(L.c_int32_p), res,
+                                    idx.ctypes.data_as(L.c_int32_p), int(chunk), int(model_chunk),
+                                    _DEFAULT_DEVICE if device is None else int(device)))
+    out = []
+    for p in range(P):
+        n = offs[p + 1] - offs[p]
+        r = SelectResult()
+        r.index = int(res[p].best_index)
+        r.model = candidates[p][r.index] if r.index >= 0 else None
+        r.score = float(res[p].best_score)
+        base = 3 * offs[p]
+        r.inlier_indices = [idx[base + t * n: base + t * n + res[p].num_inliers[t]].copy() for t in range(3)]
+        r.norm_scale = float(res[p].norm_scale)
+        if with_scores:
+            r.scores = scores[moffs[p]:moffs[p + 1]].copy()
+        if with_counts:
+            r.counts = counts[3 * moffs[p]:3 * moffs[p + 1]].reshape(-1, 3).copy()
+        out.append(r)
+    return out
+
+
 def lm_refine_batch(variant, x0, x1, depth0, depth1, min_depth, cam0, cam1, options, est_config, problems,
                     device=None, on_host=False):
     """Batched device LM (the LO's Ceres solves, src/optimizer.h:48-125 over

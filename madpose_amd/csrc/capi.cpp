@@ -10,6 +10,7 @@
 #include "../../include/madpose_mi355x.h"
 #include "host/engine.h"
 #include "host/rng.h"
+#include "host/select_plan.h"
 
 namespace {
 
@@ -196,6 +197,48 @@ int mp_refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, cons
         mp::refine_batch(variant, num_pairs, offsets, x0, x1, d0, d1, min_depth, cam0, cam1, to_opts(options),
                          to_cfg(config), rounds, reinterpret_cast<mp::Model *>(models),
                          reinterpret_cast<mp::RefineResult *>(results), inlier_idx, chunk, device);
+        return MP_OK;
+    });
+}
+
+int mp_select_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                    const double *d0, const double *d1, const double *cam0, const double *cam1,
+                    const mp_ransac_options *options, const mp_estimator_config *config,
+                    const int64_t *model_offsets, const mp_model *models, double *scores, int32_t *counts,
+                    mp_select_result *results, int32_t *inlier_idx, int64_t chunk, int64_t model_chunk, int device) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::Model) == sizeof(mp_model), "model layout");
+        static_assert(sizeof(mp::SelectResult) == sizeof(mp_select_result) && sizeof(mp_select_result) == 32,
+                      "select result layout");
+        static_assert(mp::kSelectSlabModels == MP_SELECT_SLAB_MODELS && mp::kSelectTile == MP_SELECT_TILE,
+                      "select constants");
+        if (!options) throw std::invalid_argument("null options");
+        mp::select_batch(variant, num_pairs, offsets, x0, x1, d0, d1, cam0, cam1, to_opts(options), to_cfg(config),
+                         model_offsets, reinterpret_cast<const mp::Model *>(models), scores, counts,
+                         reinterpret_cast<mp::SelectResult *>(results), inlier_idx, chunk, model_chunk, device);
+        return MP_OK;
+    });
+}
+
+int mp_debug_select_tile(int tile) {
+    int prev = -1;
+    const int r = guarded([&]() {
+        prev = mp::select_tile_override(tile);
+        return MP_OK;
+    });
+    return r == MP_OK ? prev : -1;
+}
+
+int mp_debug_select_timing(double *out_ms) {
+    return guarded([&]() {
+        if (!out_ms) throw std::invalid_argument("null output");
+        const mp::SelectTiming t = mp::select_timing_last();
+        out_ms[0] = t.pairs_ms;
+        out_ms[1] = t.prepare_ms;
+        out_ms[2] = t.upload_ms;
+        out_ms[3] = t.score_ms;
+        out_ms[4] = t.argmin_ms;
+        out_ms[5] = t.winners_ms;
         return MP_OK;
     });
 }

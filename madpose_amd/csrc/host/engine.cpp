@@ -48,6 +48,7 @@
 #include "env.h"
 #include "lo_sweep.h"
 #include "refine_plan.h"
+#include "select_plan.h"
 #include "rng.h"
 #include "solve_batch_pack.h"
 
@@ -2732,6 +2733,317 @@ void refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const 
             }
         }
         MP_HIP(hipStreamSynchronize(stream));
+    }
+}
+
+namespace {
+// page-locked host memory freed on scope exit
+template <class T> struct PinnedArray {
+    T *p = nullptr;
+    explicit PinnedArray(size_t n) { MP_HIP(hipHostMalloc((void **)&p, sizeof(T) * std::max<size_t>(n, 1))); }
+    ~PinnedArray() {
+        if (p) hipHostFree(p);
+    }
+    PinnedArray(const PinnedArray &) = delete;
+    PinnedArray &operator=(const PinnedArray &) = delete;
+};
+struct EventHolder {
+    hipEvent_t e = nullptr;
+    EventHolder() { MP_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming)); }
+    ~EventHolder() {
+        if (e) hipEventDestroy(e);
+    }
+    EventHolder(const EventHolder &) = delete;
+    EventHolder &operator=(const EventHolder &) = delete;
+};
+std::atomic<int> g_select_tile{0}; // 0: kSelectTile (select_tile_override)
+std::mutex g_select_mu;
+SelectTiming g_select_timing;
+constexpr int kSelectPrepThreads = 8;         // host threads of a slab's record preparation
+constexpr int64_t kSelectPrepPerThread = 2048; // candidates a thread is started for
+} // namespace
+
+int select_tile_override(int tile) {
+    if (tile != 0 && tile != 1 && tile != 2 && tile != 4 && tile != 8)
+        throw std::invalid_argument("tile must be 0 (the default), 1, 2, 4 or 8");
+    return g_select_tile.exchange(tile);
+}
+SelectTiming select_timing_last() {
+    std::lock_guard<std::mutex> lk(g_select_mu);
+    return g_select_timing;
+}
+
+// Ranking of given candidate models over many pairs (mp_select_batch).  The pairs of a run
+// (host/refine_plan.h) are resident at once.  Per run: the candidates' score records,
+// prepared on the host (prepare_score_rec: mp_score_models' bits), go to the device in
+// slabs (host/select_plan.h), one select_score launch each; one select_argmin launch over
+// the run's scores; the winners' inlier lists by refine_batch's sweep.  Two record
+// buffers: slab k + 1 is prepared and uploaded while slab k is scored.
+void select_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                  const double *d0, const double *d1, const double *cam0, const double *cam1,
+                  const RansacOptions &opts, const EstimatorConfig &cfg, const int64_t *model_offsets,
+                  const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
+                  int64_t chunk, int64_t model_chunk, int device) {
+    if (variant < 0 || variant > 3)
+        throw std::invalid_argument("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)");
+    if (num_pairs < 0) throw std::invalid_argument("negative pair count");
+    if (chunk < 0) throw std::invalid_argument("chunk must not be negative");
+    if (model_chunk < 0) throw std::invalid_argument("model_chunk must not be negative");
+    {
+        PairInput none; // (the option checks of every entry point)
+        validate(none, opts);
+    }
+    if (num_pairs == 0) return;
+    if (!offsets || !model_offsets || !cam0 || !cam1 || !results)
+        throw std::invalid_argument("null offsets, model_offsets, cameras or results");
+    if (offsets[0] < 0 || model_offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+    for (int32_t p = 0; p < num_pairs; ++p) {
+        if (offsets[p + 1] < offsets[p] || model_offsets[p + 1] < model_offsets[p])
+            throw std::invalid_argument("offsets must not decrease");
+        if (offsets[p + 1] - offsets[p] > kRefinePairMax) throw std::invalid_argument("pair too large");
+    }
+    if (model_offsets[num_pairs] - model_offsets[0] > kSelectModelsMax)
+        throw std::invalid_argument("more than 2^28 candidates");
+    if (offsets[num_pairs] > 0 && (!x0 || !x1 || !d0 || !d1)) throw std::invalid_argument("null input array");
+    if (model_offsets[num_pairs] > model_offsets[0] && !models) throw std::invalid_argument("null models");
+
+    const int nc = (variant == kCal || variant == kScaleOnly) ? 9 : 2;
+    const int v = variant == kScaleOnly ? kCal : variant;
+    const int tile_set = g_select_tile.load();
+    const int tile = tile_set ? tile_set : kSelectTile;
+    const bool timed = g_prof_on.load();
+    SelectTiming tm;
+    CtxLease lease(device);
+    hipStream_t stream = lease.c->stream;
+    // (timed: every stage is waited for, so the parts add up and nothing overlaps)
+    auto stage_end = [&](Clock::time_point t0, double &ms) {
+        if (!timed) return;
+        MP_HIP(hipStreamSynchronize(stream));
+        ms += 1e3 * secs(t0);
+    };
+
+    for (const RefineRun &run : refine_plan(num_pairs, offsets, chunk)) {
+        const int np = run.p1 - run.p0;
+        const int64_t T = run.total;
+        const int64_t *moff = model_offsets + run.p0; // np + 1 values; candidate 0 of the run at moff[0]
+        const int64_t M = moff[np] - moff[0];
+        // ---- problems, packed upload, pair records (as refine_batch; one list buffer) ----
+        Clock::time_point t0 = Clock::now();
+        std::vector<double> norm(np);
+        std::vector<PairData> Dh(np);
+        std::vector<PairConst> Ch(np);
+        std::vector<int64_t> off(np), list_off(np), moff_run(np + 1);
+        std::vector<double> stage(6 * (size_t)T);
+        DevArray<double> d_data((size_t)kRefineRows * T);
+        DevArray<int> d_lists(3 * (size_t)T);
+        for (int k = 0; k < np; ++k) {
+            const int32_t p = run.p0 + k;
+            const int64_t o = offsets[p], n = offsets[p + 1] - o;
+            PairInput in;
+            in.variant = variant;
+            in.n = n;
+            in.x0 = x0 + 2 * o;
+            in.x1 = x1 + 2 * o;
+            in.d0 = d0 + o;
+            in.d1 = d1 + o;
+            std::memcpy(in.cam0, cam0 + (size_t)nc * p, sizeof(double) * nc);
+            std::memcpy(in.cam1, cam1 + (size_t)nc * p, sizeof(double) * nc);
+            const Problem P = make_problem(in, opts, cfg);
+            off[k] = o - offsets[run.p0];
+            list_off[k] = 3 * off[k];
+            refine_pack_pair(P.H.x0.data(), P.H.x1.data(), P.H.d0.data(), P.H.d1.data(), n, off[k], stage.data());
+            const double *rows[kRefineRows];
+            for (int r = 0; r < kRefineRows; ++r) rows[r] = d_data.p + refine_row(T, off[k], n, r);
+            PairData &D = Dh[k];
+            D.x0u = rows[0];
+            D.x0v = rows[1];
+            D.x1u = rows[2];
+            D.x1v = rows[3];
+            D.d0 = rows[4];
+            D.d1 = rows[5];
+            D.r0 = rows[6];
+            D.r1 = rows[7];
+            D.a0 = rows[8];
+            D.a1 = rows[9];
+            D.b0 = rows[10];
+            D.b1 = rows[11];
+            Ch[k] = P.C;
+            norm[k] = P.norm_scale;
+        }
+        for (int k = 0; k <= np; ++k) moff_run[k] = moff[k] - moff[0];
+        DevArray<PairData> d_D(np);
+        DevArray<PairConst> d_C(np);
+        DevArray<int64_t> d_list_off(np), d_moff(np + 1);
+        if (T > 0)
+            MP_HIP(hipMemcpyAsync(d_data.p, stage.data(), sizeof(double) * 6 * (size_t)T, hipMemcpyHostToDevice,
+                                  stream));
+        MP_HIP(hipMemcpyAsync(d_D.p, Dh.data(), sizeof(PairData) * np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_C.p, Ch.data(), sizeof(PairConst) * np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_list_off.p, list_off.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_moff.p, moff_run.data(), sizeof(int64_t) * (np + 1), hipMemcpyHostToDevice, stream));
+        if (v == kCal)
+            for (int k = 0; k < np; ++k) {
+                double *base = d_data.p;
+                const int64_t n = Ch[k].n;
+                auto row = [&](int r) { return base + refine_row(T, off[k], n, r); };
+                MP_HIP(launch_prep_pair(stream, Ch[k], Dh[k], row(6), row(7), row(8), row(9), row(10), row(11)));
+            }
+        stage_end(t0, tm.pairs_ms);
+
+        // the model of candidate m of the run in problem units, and its pair
+        auto problem_model = [&](int k, int64_t m) {
+            Model c = models[moff[0] + m];
+            if (variant == kSF || variant == kTF) {
+                c.focal0 /= norm[k];
+                c.focal1 /= norm[k];
+            }
+            return c;
+        };
+        // ---- the candidates' scores and counts, slab by slab ----
+        DevArray<double> d_scores((size_t)M);
+        DevArray<int> d_counts(3 * (size_t)M);
+        const std::vector<SelectSlab> slabs = select_slabs(M, model_chunk);
+        const size_t cap = slabs.empty() ? 0 : (size_t)(slabs[0].m1 - slabs[0].m0); // (the first is the largest)
+        const int nbuf = slabs.size() > 1 ? 2 : 1;
+        // (a work item holds at least one candidate: a slab has at most `cap` items)
+        std::unique_ptr<PinnedArray<ScoreRec>> h_recs[2];
+        std::unique_ptr<PinnedArray<SelectItem>> h_items[2];
+        std::unique_ptr<DevArray<ScoreRec>> d_recs[2];
+        std::unique_ptr<DevArray<SelectItem>> d_items[2];
+        std::unique_ptr<EventHolder> uploaded[2], scored[2];
+        for (int b = 0; b < nbuf && cap > 0; ++b) {
+            h_recs[b].reset(new PinnedArray<ScoreRec>(cap));
+            h_items[b].reset(new PinnedArray<SelectItem>(cap));
+            d_recs[b].reset(new DevArray<ScoreRec>(cap));
+            d_items[b].reset(new DevArray<SelectItem>(cap));
+            uploaded[b].reset(new EventHolder());
+            scored[b].reset(new EventHolder());
+        }
+        std::vector<SelectItem> items;
+        for (size_t si = 0; si < slabs.size(); ++si) {
+            const SelectSlab &s = slabs[si];
+            const int b = (int)(si % 2) % nbuf;
+            const int64_t ns = s.m1 - s.m0;
+            // (the host buffers' previous upload and the device buffers' previous launch are over)
+            if (si >= 2) {
+                MP_HIP(hipEventSynchronize(uploaded[b]->e));
+                MP_HIP(hipEventSynchronize(scored[b]->e));
+            }
+            t0 = Clock::now();
+            select_items(np, moff, s, tile, items);
+            std::memcpy(h_items[b]->p, items.data(), sizeof(SelectItem) * items.size());
+            ScoreRec *recs = h_recs[b]->p;
+            // candidates a .. e - 1 of the slab; the pair of each by a walk from the first one's
+            auto prepare = [&](int64_t a, int64_t e) {
+                int k = (int)(std::upper_bound(moff_run.begin(), moff_run.end(), s.m0 + a) - moff_run.begin()) - 1;
+                for (int64_t j = a; j < e; ++j) {
+                    const int64_t m = s.m0 + j;
+                    while (moff_run[k + 1] <= m) ++k;
+                    const Model c = problem_model(k, m);
+                    prepare_score_rec(Ch[k], c, recs[j]);
+                }
+            };
+            const int nthr = (int)std::min<int64_t>(kSelectPrepThreads, ns / kSelectPrepPerThread);
+            if (nthr <= 1) {
+                prepare(0, ns);
+            } else {
+                std::vector<std::thread> threads;
+                for (int t = 1; t < nthr; ++t) threads.emplace_back(prepare, ns * t / nthr, ns * (t + 1) / nthr);
+                prepare(0, ns / nthr);
+                for (auto &t : threads) t.join();
+            }
+            if (timed) tm.prepare_ms += 1e3 * secs(t0);
+            t0 = Clock::now();
+            MP_HIP(hipMemcpyAsync(d_recs[b]->p, recs, sizeof(ScoreRec) * (size_t)ns, hipMemcpyHostToDevice, stream));
+            MP_HIP(hipMemcpyAsync(d_items[b]->p, h_items[b]->p, sizeof(SelectItem) * items.size(),
+                                  hipMemcpyHostToDevice, stream));
+            MP_HIP(hipEventRecord(uploaded[b]->e, stream));
+            stage_end(t0, tm.upload_ms);
+            t0 = Clock::now();
+            MP_HIP(launch_select_score(stream, v, tile, d_D.p, d_C.p, d_items[b]->p, (int)items.size(), d_recs[b]->p,
+                                       s.m0, d_scores.p, d_counts.p));
+            MP_HIP(hipEventRecord(scored[b]->e, stream));
+            stage_end(t0, tm.score_ms);
+        }
+        // ---- the best candidate of every pair ----
+        t0 = Clock::now();
+        DevArray<SelectBest> d_best(np);
+        std::vector<SelectBest> best(np);
+        MP_HIP(launch_select_argmin(stream, d_moff.p, np, d_scores.p, d_best.p));
+        MP_HIP(hipMemcpyAsync(best.data(), d_best.p, sizeof(SelectBest) * np, hipMemcpyDeviceToHost, stream));
+        if (scores && M > 0)
+            MP_HIP(hipMemcpyAsync(scores + moff[0], d_scores.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost,
+                                  stream));
+        if (counts && M > 0)
+            MP_HIP(hipMemcpyAsync(counts + 3 * moff[0], d_counts.p, sizeof(int) * 3 * (size_t)M,
+                                  hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+        if (timed) tm.argmin_ms += 1e3 * secs(t0);
+        // ---- the winners' lists: refine_batch's sweep, one item per pair with a winner ----
+        t0 = Clock::now();
+        std::vector<RefineItem> ritems;
+        std::vector<ScoreRec> rrecs;
+        std::vector<int> which;
+        for (int k = 0; k < np; ++k) {
+            SelectResult &R = results[run.p0 + k];
+            std::memset(&R, 0, sizeof(R));
+            R.best_score = DBL_MAX;
+            R.norm_scale = norm[k];
+            R.best_index = -1;
+            if (best[k].index < 0) continue;
+            if (best[k].index >= moff[k + 1] - moff[k]) throw std::runtime_error("select_argmin: index out of range");
+            RefineItem it;
+            it.pair = k;
+            it.buf = 0;
+            ritems.push_back(it);
+            rrecs.emplace_back();
+            prepare_score_rec(Ch[k], problem_model(k, moff_run[k] + best[k].index), rrecs.back());
+            which.push_back(k);
+        }
+        const size_t nw = which.size();
+        if (nw > 0) {
+            DevArray<RefineItem> d_ritems(nw);
+            DevArray<ScoreRec> d_rrecs(nw);
+            DevArray<RefineSweepOut> d_out(nw);
+            std::vector<RefineSweepOut> outs(nw);
+            MP_HIP(hipMemcpyAsync(d_ritems.p, ritems.data(), sizeof(RefineItem) * nw, hipMemcpyHostToDevice, stream));
+            MP_HIP(hipMemcpyAsync(d_rrecs.p, rrecs.data(), sizeof(ScoreRec) * nw, hipMemcpyHostToDevice, stream));
+            MP_HIP(launch_refine_sweep(stream, v, d_D.p, d_C.p, d_ritems.p, d_rrecs.p, (int)nw, d_list_off.p,
+                                       d_lists.p, 3 * T, d_out.p));
+            MP_HIP(hipMemcpyAsync(outs.data(), d_out.p, sizeof(RefineSweepOut) * nw, hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipStreamSynchronize(stream));
+            for (size_t j = 0; j < nw; ++j) {
+                const int k = which[j];
+                SelectResult &R = results[run.p0 + k];
+                // (the same record through the same arithmetic: anything else is a defect; the
+                // measurement hook's other work-item sizes are not pinned to these bits)
+                if (tile == kSelectTile && std::memcmp(&outs[j].score, &best[k].score, sizeof(double)) != 0)
+                    throw std::runtime_error("select_batch: the winner's sweep score differs from its selected score");
+                R.best_score = best[k].score;
+                R.best_index = best[k].index;
+                for (int t = 0; t < 3; ++t) R.num_inliers[t] = outs[j].count[t];
+            }
+            if (inlier_idx && T > 0) {
+                std::vector<int> lists(3 * (size_t)T);
+                MP_HIP(hipMemcpyAsync(lists.data(), d_lists.p, sizeof(int) * lists.size(), hipMemcpyDeviceToHost,
+                                      stream));
+                MP_HIP(hipStreamSynchronize(stream));
+                for (int k : which) {
+                    const int32_t p = run.p0 + k;
+                    const int64_t n = Ch[k].n;
+                    for (int t = 0; t < 3; ++t)
+                        std::memcpy(inlier_idx + 3 * offsets[p] + t * n,
+                                    lists.data() + refine_list(T, off[k], n, 0, t),
+                                    sizeof(int) * (size_t)results[p].num_inliers[t]);
+                }
+            }
+        }
+        if (timed) tm.winners_ms += 1e3 * secs(t0);
+        MP_HIP(hipStreamSynchronize(stream));
+    }
+    if (timed) {
+        std::lock_guard<std::mutex> lk(g_select_mu);
+        g_select_timing = tm;
     }
 }
 

@@ -113,6 +113,44 @@ void refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const 
                   const RansacOptions &opts, const EstimatorConfig &cfg, int rounds, Model *models,
                   RefineResult *results, int32_t *inlier_idx, int64_t chunk, int device);
 
+// Ranking of given candidate models over many pairs on the device (mp_select_batch).
+// Pairs laid out as refine_batch's, without min_depth (no score depends on it); pair p's
+// candidates are models[model_offsets[p] .. model_offsets[p + 1]), user units.  Per
+// candidate: the score score_models gives for it in problem units (the record prepared on
+// the host, the same bits) and the three counts of errors (score_models') below
+// PairConst::thr -- scores[m] / counts[3 m + t] for m the candidate's index into models,
+// both nullable.  Per pair: GetBestEstimatedModelId's walk (start at DBL_MAX, strict <)
+// over its scores, and the winner's three ascending inlier lists as refine_batch forms
+// them (inlier_idx, nullable, its layout).  Runs of `chunk` pairs as refine_batch; the
+// records of `model_chunk` candidates (0: host/select_plan.h's default) are on the device
+// at once.  Results depend on neither.
+struct SelectResult {
+    double best_score, norm_scale; // best_score DBL_MAX when no candidate won
+    int32_t best_index;            // within the pair's candidates; -1: none
+    int32_t num_inliers[3];        // the winner's lists
+};
+void select_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                  const double *d0, const double *d1, const double *cam0, const double *cam1,
+                  const RansacOptions &opts, const EstimatorConfig &cfg, const int64_t *model_offsets,
+                  const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
+                  int64_t chunk, int64_t model_chunk, int device);
+// Measurement hooks of select_batch (mp_debug_select_tile, mp_debug_select_timing).
+// select_tile_override: candidates per work item of the following calls (1, 2, 4, 8; 0:
+// the built-in kSelectTile, the only size pinned to score_models' bits); returns the
+// previous setting.  select_timing_last: the stage
+// times of the last call made while profiling was enabled (profile_enable), every stage
+// waited for, so nothing overlaps.
+struct SelectTiming {
+    double pairs_ms = 0;   // make_problem, the packed upload, the pair preparation
+    double prepare_ms = 0; // host: the work items and prepare_score_rec of every slab
+    double upload_ms = 0;  // records and items to the device
+    double score_ms = 0;   // select_score
+    double argmin_ms = 0;  // select_argmin and the copy back of its results (scores, counts)
+    double winners_ms = 0; // the winners' records, refine_sweep, lists back
+};
+int select_tile_override(int tile);
+SelectTiming select_timing_last();
+
 // Standalone solvers on the device (mp_solve_* / mp_relpose_5pt).
 // alt: 0 default MD solver, 1 use_ours, 2 use_4p4d (two-focal)
 int solve_md_direct(int variant, const double *x, const double *y, const double *dx, const double *dy, double *sols,

@@ -139,6 +139,18 @@ struct RefineSweepOut {
     double score;
     int count[3], pad;
 };
+// One workgroup of select_score_kernel (kernels/select_batch.h; planned by
+// host/select_plan.h): `count` consecutive candidates of pair `pair` (of the run), their
+// records at rec .. rec + count - 1 of the slab on the device.
+struct SelectItem {
+    int pair, rec, count, pad;
+};
+// select_argmin_kernel's outcome per pair: the walk of GetBestEstimatedModelId over the
+// pair's candidates (index within the pair, -1: none won; score DBL_MAX then).
+struct SelectBest {
+    double score;
+    int index, pad;
+};
 
 constexpr int kMaxModelsCal = 10; // MD <= 4, 5pt <= 10
 constexpr int kMaxModelsSF = 16;  // MD <= 8, 6pt <= 15

@@ -133,6 +133,17 @@ hipError_t launch_refine_sweep(hipStream_t s, int variant, const PairData *Ds, c
 hipError_t launch_lm_pairs(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs, const LmJob *jobs,
                            const LmPairRef *refs, int njobs, const int *idx, Model *out, int *status);
 
+// Ranking of candidates over the resident pairs (select_batch.h; mp_select_batch).
+// Work item k = items[k].count (<= tile) candidates of pair items[k].pair with the records
+// recs[items[k].rec ..]; candidate j of the item has position at = base + items[k].rec + j
+// in the run: scores[at] = its score as launch_score_models gives it, counts[3 at + t] =
+// the number of errors (launch_sweep's) below thr[t].  tile: 1, 2, 4 or 8.
+hipError_t launch_select_score(hipStream_t s, int variant, int tile, const PairData *Ds, const PairConst *Cs,
+                               const SelectItem *items, int nitems, const ScoreRec *recs, int64_t base,
+                               double *scores, int *counts);
+// out[k] = GetBestEstimatedModelId's walk over scores[moff[k] .. moff[k + 1]) (np pairs)
+hipError_t launch_select_argmin(hipStream_t s, const int64_t *moff, int np, const double *scores, SelectBest *out);
+
 // squared Bougnoux focals of k fundamental matrices (9 doubles each) into out (2 each)
 hipError_t launch_bougnoux(hipStream_t s, const double *F, int64_t k, double *out);
 

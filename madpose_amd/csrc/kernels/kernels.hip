@@ -1746,3 +1746,5 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 #include "solve_batch.h"
 // refinement of given models over many resident pairs (mp_refine_batch)
 #include "refine_batch.h"
+// ranking of candidate models over many resident pairs (mp_select_batch)
+#include "select_batch.h"
