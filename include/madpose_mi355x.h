@@ -317,6 +317,51 @@ int mp_select_batch(int variant, int32_t num_pairs, const int64_t *offsets, cons
 int mp_debug_select_tile(int tile);
 int mp_debug_select_timing(double *out_ms /* 6 */);
 
+/* The estimators' sample models over many pairs: for explicit minimal samples, exactly the
+ * models the estimator's MinimalSolver stage generates for them, one launch sequence for all
+ * pairs, in the form mp_select_batch takes.  Pair layout, `chunk` and its default run bound
+ * as mp_refine_batch.  Pair p's samples are s = sample_offsets[p] .. sample_offsets[p + 1] - 1:
+ * sample_types[s] 0 (the MD solver) or 1 (the point solver), sample_idx[8 s ..] its indices
+ * within the pair -- a type-0 sample reads its first 3 (calibrated) or 4, a type-1 sample
+ * its first 5 (calibrated), 6 (shared focal) or 7 (two focal); the other slots are ignored.
+ * Sample s gets counts[s] models in models[s * slots ..], slots = MP_HYPOTHESIZE_SLOTS_*
+ * of the variant, in the estimator's order: the models the estimator puts in the
+ * iteration's model slots for the same pair, options, config, solver type and sample (the
+ * ones MADPOSE_MODEL_DUMP records), all 17 doubles bit for bit -- type 0 the exact MD
+ * solver with the estimator's min-depth filter, type 1 5pt / 6pt / 7pt with pose recovery,
+ * depth tail, compaction and the shared-focal duplicate rule.  Models leave in user units,
+ * as mp_estimate returns them: for shared and two focal each focal is the problem-unit
+ * focal times the pair's norm_scale (one IEEE product).  Slots from counts[s] on are zero.
+ * Results depend on neither chunk nor sample_chunk (samples on the device at once; 0:
+ * MP_HYPOTHESIZE_SLAB_SAMPLES, values above 131072 act as 131072), nor on the other pairs
+ * or samples of the call.  norm_scale (nullable): one per pair.
+ * Supported: MP_CALIBRATED, MP_SHARED_FOCAL, MP_TWO_FOCAL with use_shift on and without
+ * use_ours / use_4p4d; MP_SCALE_ONLY, use_shift = 0 and the alternates give MP_EINVAL.
+ * min_depth and min_depth_constraint are honoured.  Checked on the host before any device
+ * call, MP_EINVAL: a bad variant, negative counts, decreasing or negative offsets or
+ * sample_offsets, more than 2^22 samples, null required pointers, chunk < 0, sample_chunk
+ * < 0, a type other than 0 or 1, a read index outside [0, n_p), a repeated index within a
+ * sample, a sample on a pair too small for its solver.  num_pairs == 0, and zero samples
+ * once the arguments are valid, return MP_OK without touching the device. */
+#define MP_HYPOTHESIZE_SLAB_SAMPLES 32768
+#define MP_HYPOTHESIZE_SLOTS_CALIBRATED 10
+#define MP_HYPOTHESIZE_SLOTS_SHARED_FOCAL 16
+#define MP_HYPOTHESIZE_SLOTS_TWO_FOCAL 4
+int mp_hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                         const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                         const double *cam1, const mp_ransac_options *options, const mp_estimator_config *config,
+                         const int64_t *sample_offsets /* num_pairs + 1 */,
+                         const int32_t *sample_types /* S: 0 the MD solver, 1 the point solver */,
+                         const int32_t *sample_idx /* S x 8, indices within the pair; unused slots ignored */,
+                         mp_model *models /* S x slots(variant) */, int32_t *counts /* S */,
+                         double *norm_scale /* nullable, one per pair */, int64_t chunk, int64_t sample_chunk,
+                         int device);
+/* Measurement hook (tools/hypothesize_batch_bench.py): five stage times in ms of the last
+ * mp_hypothesize_batch call made while profiling was enabled (mp_profile_enable) -- pair
+ * setup, host planning, uploads, the solve launches, the copies back; every stage is waited
+ * for then. */
+int mp_debug_hypothesize_timing(double *out_ms /* 5 */);
+
 /* bougnoux_focals (src/hybrid_pose_two_focal_estimator.cpp:11-32; numpy twin
  * madpose/utils.py:25-56 bougnoux_numpy with p1 = p2 = 0): squared focal lengths
  * (f0^2, f1^2) of k fundamental matrices F (k x 9, row-major) into out (k x 2), on

@@ -26,6 +26,7 @@ from .api import (  # noqa: F401
     bougnoux_focals_batch,
     lm_refine_batch,
     get_depths_batch,
+    hypothesize_batch,
     pose_auc_batch,
     pose_eval_batch,
     poses_from_models,

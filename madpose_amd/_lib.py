@@ -22,6 +22,10 @@ REFINE_RUN_CORRESPONDENCES = 1 << 22
 # mp_select_batch: candidates per record slab when model_chunk == 0; candidates per device
 # work item (MP_SELECT_SLAB_MODELS, MP_SELECT_TILE)
 SELECT_SLAB_MODELS, SELECT_TILE = 1 << 16, 1
+# mp_hypothesize_batch: samples per slab when sample_chunk == 0, samples per call, index
+# slots per sample, model slots per sample by variant (MP_HYPOTHESIZE_*)
+HYPOTHESIZE_SLAB_SAMPLES, HYPOTHESIZE_MAX_SAMPLES, HYPOTHESIZE_SAMPLE_STRIDE = 32768, 1 << 22, 8
+HYPOTHESIZE_SLOTS = (10, 16, 4)
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -150,6 +154,12 @@ EXPORTS = {
                                        ctypes.POINTER(mp_estimator_config), c_int64_p, ctypes.POINTER(mp_model),
                                        c_double_p, c_int32_p, ctypes.POINTER(mp_select_result), c_int32_p,
                                        ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "mp_hypothesize_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
+                                            c_double_p, c_double_p, c_double_p, c_double_p,
+                                            ctypes.POINTER(mp_ransac_options), ctypes.POINTER(mp_estimator_config),
+                                            c_int64_p, c_int32_p, c_int32_p, ctypes.POINTER(mp_model), c_int32_p,
+                                            c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
+    "mp_debug_hypothesize_timing": (ctypes.c_int, [c_double_p]),
     "mp_debug_select_tile": (ctypes.c_int, [ctypes.c_int]),
     "mp_debug_select_timing": (ctypes.c_int, [c_double_p]),
     "mp_refine_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,

@@ -528,15 +528,18 @@ def select_batch(variant, pairs, candidates, options, est_config=None, with_scor
                  chunk=0, model_chunk=0, device=None):
     """Rank candidate poses over many pairs on the device (mp_select_batch).
 
-    pairs: estimate_batch's dicts; candidates: one sequence of pose objects per pair, as
-    the estimators return them (user units); a sequence may be empty.  Every candidate gets
+    pairs: estimate_batch's dicts; candidates: per pair one sequence of pose objects, as
+    the estimators return them (user units), or one float64 array of shape (K, 17), a model
+    per row in mp_model field order as hypothesize_batch and solve_scale_shift_pose_batch
+    return them; either may be empty.  Every candidate gets
     the estimators' MSAC score (score_models' value for it, bit for bit) and the three
     counts of errors below the thresholds; per pair the first candidate with the lowest
     score wins (the reference's GetBestEstimatedModelId: strict <, a NaN or infinite score
     never wins).  All pairs of a run of `chunk` pairs (0: refine_batch's default bound) are
     resident at once; the score records of `model_chunk` candidates (0: the default) are on
     the device at a time; results depend on neither.  Returns one SelectResult per pair:
-    index (-1: no winner), model (the chosen candidate object itself, or None), score
+    index (-1: no winner), model (the chosen candidate object itself -- for an array entry
+    the winning row as a pose object, poses_from_models' -- or None), score
     (DBL_MAX without a winner), inlier_indices (three int32 arrays, the winner's, as
     refine_batch would form them), norm_scale, scores (float64, one per candidate, with
     with_scores, else None) and counts (int32 K x 3, with with_counts, else None)."""
@@ -570,6 +573,9 @@ def select_batch(variant, pairs, candidates, options, est_config=None, with_scor
         c0s.append(np.asarray(p[k0], dtype=np.float64).reshape(ncam))
         c1s.append(np.asarray(p[k1], dtype=np.float64).reshape(ncam))
         offs.append(offs[-1] + n)
+        if isinstance(cands, np.ndarray):
+            if cands.dtype != np.float64 or cands.ndim != 2 or cands.shape[1] != 17:
+                raise ValueError(f"array candidates must be float64 of shape (K, 17), got {cands.dtype} {cands.shape}")
         moffs.append(moffs[-1] + len(cands))
     cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
     X0, X1, D0, D1, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, c0s, c1s))
@@ -578,7 +584,19 @@ def select_batch(variant, pairs, candidates, options, est_config=None, with_scor
     offsets = np.asarray(offs, dtype=np.int64)
     model_offsets = np.asarray(moffs, dtype=np.int64)
     M = moffs[-1]
-    arr = (L.mp_model * max(M, 1))(*[_model_to_c(m, variant) for cands in candidates for m in cands])
+    if any(isinstance(cands, np.ndarray) for cands in candidates):
+        # (rows copied as they are; objects through _model_to_c, the same bytes as below)
+        rows = np.zeros((max(M, 1), 17))
+        for p, cands in enumerate(candidates):
+            if isinstance(cands, np.ndarray):
+                rows[moffs[p]:moffs[p + 1]] = cands
+            else:
+                for j, m in enumerate(cands):
+                    c_m = _model_to_c(m, variant)
+                    ctypes.memmove(rows[moffs[p] + j].ctypes.data, ctypes.byref(c_m), ctypes.sizeof(c_m))
+        arr = rows.ctypes.data_as(ctypes.POINTER(L.mp_model))
+    else:
+        arr = (L.mp_model * max(M, 1))(*[_model_to_c(m, variant) for cands in candidates for m in cands])
     res = (L.mp_select_result * P)()
     idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
     scores = np.zeros(max(M, 1), dtype=np.float64) if with_scores else None
@@ -595,7 +613,10 @@ def select_batch(variant, pairs, candidates, options, est_config=None, with_scor
         n = offs[p + 1] - offs[p]
         r = SelectResult()
         r.index = int(res[p].best_index)
-        r.model = candidates[p][r.index] if r.index >= 0 else None
+        if r.index >= 0 and isinstance(candidates[p], np.ndarray):
+            r.model = _pose_from_row(candidates[p][r.index], variant)
+        else:
+            r.model = candidates[p][r.index] if r.index >= 0 else None
         r.score = float(res[p].best_score)
         base = 3 * offs[p]
         r.inlier_indices = [idx[base + t * n: base + t * n + res[p].num_inliers[t]].copy() for t in range(3)]
@@ -946,6 +967,13 @@ def relpose_batch(kind, x0, x1, chunk=0, device=None):
     return models, counts
 
 
+def _pose_from_row(row, variant):
+    m = L.mp_model()
+    row = np.ascontiguousarray(row, dtype=np.float64)
+    ctypes.memmove(ctypes.byref(m), row.ctypes.data, ctypes.sizeof(m))
+    return _model_from_c(m, variant)
+
+
 def poses_from_models(models_rows, variant):
     """The rows of one sample's models (n x 17, e.g. models[b, :counts[b]]) as the pose
     objects the single-sample functions return (variant 0 / 1 / 2: PoseScaleOffset /
@@ -955,12 +983,116 @@ def poses_from_models(models_rows, variant):
     rows = np.ascontiguousarray(np.asarray(models_rows, dtype=np.float64))
     if rows.ndim != 2 or rows.shape[1] != 17:
         raise ValueError(f"models_rows must have shape (n, 17), got {rows.shape}")
-    out = []
-    for row in rows:
-        m = L.mp_model()
-        ctypes.memmove(ctypes.byref(m), row.ctypes.data, ctypes.sizeof(m))
-        out.append(_model_from_c(m, variant))
-    return out
+    return [_pose_from_row(row, variant) for row in rows]
+
+
+def hypothesize_batch(variant, pairs, samples, options, est_config=None, chunk=0, sample_chunk=0, device=None):
+    """The estimators' sample models over many pairs (mp_hypothesize_batch).
+
+    pairs: estimate_batch's dicts; samples: one (types, idx) per pair -- types int32 of
+    shape (K_p,), 0 the MD solver, 1 the point solver; idx int32 of shape (K_p, 8), indices
+    into the pair's correspondences, of which a type-0 sample reads the first 3
+    (calibrated) or 4 and a type-1 sample the first 5 / 6 / 7 (the other slots are
+    ignored); K_p may be 0.  For every sample: exactly the models the estimator's
+    MinimalSolver stage forms for that pair, options, config, solver type and sample, in
+    its order and bit for bit, in user units.  Supported: variants 0 / 1 / 2 with
+    use_shift on and without use_ours / use_4p4d.  All pairs of a run of `chunk` pairs (0:
+    refine_batch's default bound) are resident at once, `sample_chunk` samples (0: the
+    default) are on the device at a time; results depend on neither.  Returns (results,
+    norm_scale): results holds one (models, counts) per pair, models float64 of shape
+    (K_p, slots, 17) in mp_model field order (slots 10 / 16 / 4; rows from counts[k] on are
+    zero; models[k, :counts[k]] are select_batch's array candidates once flattened),
+    counts int32 of shape (K_p,); norm_scale float64, one per pair."""
+    if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL):
+        raise ValueError("variant must be 0 (calibrated), 1 (shared focal) or 2 (two focal); "
+                         "scale only is not supported")
+    if len(samples) != len(pairs):
+        raise ValueError(f"one (types, idx) per pair: {len(samples)} entries for {len(pairs)} pairs")
+    for name, val in (("chunk", chunk), ("sample_chunk", sample_chunk)):
+        if isinstance(val, bool) or not isinstance(val, (int, np.integer, float)) or int(val) != val or val < 0:
+            raise ValueError(f"{name} must be a non-negative integer (0: the default)")
+    if est_config is None:
+        est_config = EstimatorConfig()
+    if not est_config.use_shift:
+        raise ValueError("hypothesize_batch does not support use_shift = False")
+    if getattr(options, "use_ours", False) or getattr(options, "use_4p4d", False):
+        raise ValueError("hypothesize_batch does not support the alternate MD solvers (use_ours / use_4p4d)")
+    o = options._to_c()
+    c = est_config._to_c()
+    P = len(pairs)
+    if P == 0:
+        return [], np.zeros(0)
+    slots = L.HYPOTHESIZE_SLOTS[variant]
+    stride = L.HYPOTHESIZE_SAMPLE_STRIDE
+    ksz = (3 if variant == L.CALIBRATED else 4, (5, 6, 7)[variant])
+    k0, k1 = ("K0", "K1") if variant == L.CALIBRATED else ("pp0", "pp1")
+    ncam = 9 if variant == L.CALIBRATED else 2
+    x0s, x1s, d0s, d1s, mds, c0s, c1s, offs, soffs, tys, ids = [], [], [], [], [], [], [], [0], [0], [], []
+    for p, (pair, smp) in enumerate(zip(pairs, samples)):
+        x0 = _pts(pair["x0"], "x0")
+        n = x0.shape[0]
+        x1 = _pts(pair["x1"], "x1")
+        if x1.shape[0] != n:
+            raise ValueError("x0 and x1 must have the same number of rows")
+        x0s.append(x0.reshape(-1))
+        x1s.append(x1.reshape(-1))
+        d0s.append(_vec(pair["depth0"], n, "depth0"))
+        d1s.append(_vec(pair["depth1"], n, "depth1"))
+        mds.append(np.asarray(pair.get("min_depth", (0.0, 0.0)), dtype=np.float64).reshape(2))
+        c0s.append(np.asarray(pair[k0], dtype=np.float64).reshape(ncam))
+        c1s.append(np.asarray(pair[k1], dtype=np.float64).reshape(ncam))
+        offs.append(offs[-1] + n)
+        try:
+            types, idx = smp
+        except (TypeError, ValueError):
+            raise ValueError(f"pair {p}: samples must hold one (types, idx) per pair") from None
+        types, idx = np.asarray(types), np.asarray(idx)
+        if types.dtype != np.int32 or idx.dtype != np.int32:
+            raise ValueError(f"pair {p}: types and idx must be int32 arrays")
+        K = types.shape[0] if types.ndim == 1 else -1
+        if K < 0 or idx.shape != (K, stride):
+            raise ValueError(f"pair {p}: types must have shape (K,) and idx (K, {stride}), got {types.shape} "
+                             f"and {idx.shape}")
+        if K:
+            if ((types != 0) & (types != 1)).any():
+                raise ValueError(f"pair {p}: a sample's type must be 0 (MD solver) or 1 (point solver)")
+            for t in (0, 1):
+                rows = idx[types == t][:, :ksz[t]]
+                if rows.shape[0] == 0:
+                    continue
+                if n < ksz[t]:
+                    raise ValueError(f"pair {p}: {n} correspondences are too few for a type-{t} sample")
+                if (rows < 0).any() or (rows >= n).any():
+                    raise ValueError(f"pair {p}: a sample index lies outside [0, {n})")
+                srt = np.sort(rows, axis=1)
+                if (srt[:, 1:] == srt[:, :-1]).any():
+                    raise ValueError(f"pair {p}: a sample repeats an index")
+        tys.append(types)
+        ids.append(idx.reshape(-1))
+        soffs.append(soffs[-1] + K)
+    S = soffs[-1]
+    if S > L.HYPOTHESIZE_MAX_SAMPLES:
+        raise ValueError(f"at most 2^22 samples per call, got {S}")
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
+    X0, X1, D0, D1, MD, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, mds, c0s, c1s))
+    if offs[-1] == 0:  # (no correspondence at all: the arrays still need an address)
+        X0, X1, D0, D1 = np.zeros(2), np.zeros(2), np.zeros(1), np.zeros(1)
+    offsets = np.asarray(offs, dtype=np.int64)
+    sample_offsets = np.asarray(soffs, dtype=np.int64)
+    T = np.ascontiguousarray(np.concatenate(tys), dtype=np.int32) if S else np.zeros(1, dtype=np.int32)
+    I = np.ascontiguousarray(np.concatenate(ids), dtype=np.int32) if S else np.zeros(stride, dtype=np.int32)
+    models = np.zeros((max(S, 1), slots, 17))
+    counts = np.zeros(max(S, 1), dtype=np.int32)
+    norm = np.ones(P)
+    L.check(L.lib().mp_hypothesize_batch(variant, P, offsets.ctypes.data_as(L.c_int64_p), _dp(X0), _dp(X1), _dp(D0),
+                                         _dp(D1), _dp(MD), _dp(C0), _dp(C1), ctypes.byref(o), ctypes.byref(c),
+                                         sample_offsets.ctypes.data_as(L.c_int64_p), T.ctypes.data_as(L.c_int32_p),
+                                         I.ctypes.data_as(L.c_int32_p),
+                                         models.ctypes.data_as(ctypes.POINTER(L.mp_model)),
+                                         counts.ctypes.data_as(L.c_int32_p), _dp(norm), int(chunk), int(sample_chunk),
+                                         _DEFAULT_DEVICE if device is None else int(device)))
+    out = [(models[soffs[p]:soffs[p + 1]].copy(), counts[soffs[p]:soffs[p + 1]].copy()) for p in range(P)]
+    return out, norm
 
 
 def score_models(variant, x0, x1, depth0, depth1, cam0, cam1, options, est_config, models, with_errors=False,

@@ -9,6 +9,7 @@
 
 #include "../../include/madpose_mi355x.h"
 #include "host/engine.h"
+#include "host/hypothesis_plan.h"
 #include "host/rng.h"
 #include "host/select_plan.h"
 
@@ -239,6 +240,40 @@ int mp_debug_select_timing(double *out_ms) {
         out_ms[3] = t.score_ms;
         out_ms[4] = t.argmin_ms;
         out_ms[5] = t.winners_ms;
+        return MP_OK;
+    });
+}
+
+int mp_hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                         const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                         const double *cam1, const mp_ransac_options *options, const mp_estimator_config *config,
+                         const int64_t *sample_offsets, const int32_t *sample_types, const int32_t *sample_idx,
+                         mp_model *models, int32_t *counts, double *norm_scale, int64_t chunk, int64_t sample_chunk,
+                         int device) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::Model) == sizeof(mp_model), "model layout");
+        static_assert(mp::kHypSlabSamples == MP_HYPOTHESIZE_SLAB_SAMPLES &&
+                          mp::kMaxModelsCal == MP_HYPOTHESIZE_SLOTS_CALIBRATED &&
+                          mp::kMaxModelsSF == MP_HYPOTHESIZE_SLOTS_SHARED_FOCAL &&
+                          mp::kMaxModelsTF == MP_HYPOTHESIZE_SLOTS_TWO_FOCAL,
+                      "hypothesize constants");
+        if (!options) throw std::invalid_argument("null options");
+        mp::hypothesize_batch(variant, num_pairs, offsets, x0, x1, d0, d1, min_depth, cam0, cam1, to_opts(options),
+                              to_cfg(config), sample_offsets, sample_types, sample_idx,
+                              reinterpret_cast<mp::Model *>(models), counts, norm_scale, chunk, sample_chunk, device);
+        return MP_OK;
+    });
+}
+
+int mp_debug_hypothesize_timing(double *out_ms) {
+    return guarded([&]() {
+        if (!out_ms) throw std::invalid_argument("null output");
+        const mp::HypTiming t = mp::hypothesize_timing_last();
+        out_ms[0] = t.pairs_ms;
+        out_ms[1] = t.plan_ms;
+        out_ms[2] = t.upload_ms;
+        out_ms[3] = t.solve_ms;
+        out_ms[4] = t.download_ms;
         return MP_OK;
     });
 }

@@ -46,6 +46,7 @@
 #include "../kernels/kernels.h"
 #include "batch_draw.h"
 #include "env.h"
+#include "hypothesis_plan.h"
 #include "lo_sweep.h"
 #include "refine_plan.h"
 #include "select_plan.h"
@@ -3044,6 +3045,250 @@ void select_batch(int variant, int32_t num_pairs, const int64_t *offsets, const 
     if (timed) {
         std::lock_guard<std::mutex> lk(g_select_mu);
         g_select_timing = tm;
+    }
+}
+
+namespace {
+std::mutex g_hyp_mu;
+HypTiming g_hyp_timing;
+} // namespace
+
+HypTiming hypothesize_timing_last() {
+    std::lock_guard<std::mutex> lk(g_hyp_mu);
+    return g_hyp_timing;
+}
+
+// The estimators' sample models over many pairs (mp_hypothesize_batch).  Every argument is
+// checked on the host before the device is touched: a kernel only ever reads indices that
+// were range-checked here, from a copy in which the unused slots of a sample are zero.  The
+// pairs of a run (host/refine_plan.h) are resident at once, set up as refine_batch /
+// select_batch set theirs up; the run's samples go through the device in slabs
+// (host/hypothesis_plan.h), one launch_hyp_solve each.
+void hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                       const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                       const double *cam1, const RansacOptions &opts, const EstimatorConfig &cfg,
+                       const int64_t *sample_offsets, const int32_t *sample_types, const int32_t *sample_idx,
+                       Model *models, int32_t *counts, double *norm_scale, int64_t chunk, int64_t sample_chunk,
+                       int device) {
+    if (variant == kScaleOnly)
+        throw std::invalid_argument("hypothesize_batch does not support MP_SCALE_ONLY (variant 3)");
+    if (variant < 0 || variant > 2)
+        throw std::invalid_argument("variant must be 0 (calibrated), 1 (shared focal) or 2 (two focal)");
+    if (num_pairs < 0) throw std::invalid_argument("negative pair count");
+    if (chunk < 0) throw std::invalid_argument("chunk must not be negative");
+    if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
+    if (!cfg.use_shift) throw std::invalid_argument("hypothesize_batch does not support use_shift = 0");
+    if (opts.use_ours || opts.use_4p4d)
+        throw std::invalid_argument("hypothesize_batch does not support the alternate MD solvers (use_ours / use_4p4d)");
+    {
+        PairInput none; // (the option checks of every entry point)
+        validate(none, opts);
+    }
+    if (num_pairs == 0) return;
+    if (!offsets || !sample_offsets || !min_depth || !cam0 || !cam1)
+        throw std::invalid_argument("null offsets, sample_offsets, min_depth or cameras");
+    if (offsets[0] < 0 || sample_offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+    for (int32_t p = 0; p < num_pairs; ++p) {
+        if (offsets[p + 1] < offsets[p] || sample_offsets[p + 1] < sample_offsets[p])
+            throw std::invalid_argument("offsets must not decrease");
+        if (offsets[p + 1] - offsets[p] > kRefinePairMax) throw std::invalid_argument("pair too large");
+    }
+    const int64_t S_all = sample_offsets[num_pairs] - sample_offsets[0];
+    if (S_all > kHypSamplesMax) throw std::invalid_argument("more than 2^22 samples");
+    if (offsets[num_pairs] > 0 && (!x0 || !x1 || !d0 || !d1)) throw std::invalid_argument("null input array");
+    if (S_all > 0 && (!sample_types || !sample_idx || !models || !counts))
+        throw std::invalid_argument("null sample_types, sample_idx, models or counts");
+    const int v = variant;
+    const int ksz[2] = {v == kCal ? 3 : 4, v == kCal ? 5 : (v == kSF ? 6 : 7)};
+    static_assert(kSampleStride == 8, "a sample has 8 index slots (mp_hypothesize_batch)");
+    for (int32_t p = 0; p < num_pairs; ++p) {
+        const int64_t n = offsets[p + 1] - offsets[p];
+        for (int64_t s = sample_offsets[p]; s < sample_offsets[p + 1]; ++s) {
+            const int32_t t = sample_types[s];
+            if (t != 0 && t != 1)
+                throw std::invalid_argument("sample " + std::to_string(s) + ": type must be 0 (MD solver) or 1 (point solver)");
+            const int k = ksz[t];
+            if (n < k)
+                throw std::invalid_argument("sample " + std::to_string(s) + ": pair " + std::to_string(p) +
+                                            " has too few correspondences for the solver");
+            const int32_t *q = sample_idx + kSampleStride * s;
+            for (int a = 0; a < k; ++a) {
+                if (q[a] < 0 || q[a] >= n)
+                    throw std::invalid_argument("sample " + std::to_string(s) + ": index outside the pair");
+                for (int b = 0; b < a; ++b)
+                    if (q[a] == q[b])
+                        throw std::invalid_argument("sample " + std::to_string(s) + ": repeated index");
+            }
+        }
+    }
+
+    const int nc = v == kCal ? 9 : 2;
+    const int maxm = max_models(v);
+    const int cap[2] = {hyp_md_cap(v), hyp_pt_cap(v)};
+    auto pair_input = [&](int32_t p) {
+        const int64_t o = offsets[p];
+        PairInput in;
+        in.variant = variant;
+        in.n = offsets[p + 1] - o;
+        in.x0 = x0 + 2 * o;
+        in.x1 = x1 + 2 * o;
+        in.d0 = d0 + o;
+        in.d1 = d1 + o;
+        in.min_depth[0] = min_depth[2 * p];
+        in.min_depth[1] = min_depth[2 * p + 1];
+        std::memcpy(in.cam0, cam0 + (size_t)nc * p, sizeof(double) * nc);
+        std::memcpy(in.cam1, cam1 + (size_t)nc * p, sizeof(double) * nc);
+        return in;
+    };
+    if (S_all == 0) { // (no device work: the normalisation scales are host values)
+        if (norm_scale)
+            for (int32_t p = 0; p < num_pairs; ++p) norm_scale[p] = make_problem(pair_input(p), opts, cfg).norm_scale;
+        return;
+    }
+
+    const bool timed = g_prof_on.load();
+    HypTiming tm;
+    CtxLease lease(device);
+    hipStream_t stream = lease.c->stream;
+    auto stage_end = [&](Clock::time_point t0, double &ms) {
+        if (!timed) return;
+        MP_HIP(hipStreamSynchronize(stream));
+        ms += 1e3 * secs(t0);
+    };
+    // one slab's device buffers, sized for the largest slab of the call
+    const int64_t slab_cap = std::min<int64_t>(S_all, hyp_slabs(S_all, sample_chunk)[0].s1);
+    DevArray<int> d_samples((size_t)slab_cap * kSampleStride), d_list((size_t)slab_cap), d_counts((size_t)slab_cap);
+    DevArray<HypItem> d_items((size_t)slab_cap);
+    DevArray<Model> d_models((size_t)slab_cap * maxm);
+    DevArray<double> d_cand((size_t)slab_cap * kPtCandStride), d_pen(v == kSF ? (size_t)slab_cap * kPtPenStride : 1);
+    DevArray<int> d_ncand((size_t)slab_cap), d_valid((size_t)slab_cap * kPtSlotStride);
+    DevArray<Model> d_slots((size_t)slab_cap * kPtSlotStride);
+    const PtWorkspace W{d_cand.p, d_ncand.p, d_slots.p, d_valid.p, d_pen.p};
+    std::vector<int> h_samples((size_t)slab_cap * kSampleStride), h_list((size_t)slab_cap);
+    std::vector<HypItem> h_items((size_t)slab_cap);
+    HypPlan plan;
+
+    for (const RefineRun &run : refine_plan(num_pairs, offsets, chunk)) {
+        const int np = run.p1 - run.p0;
+        const int64_t T = run.total;
+        const int64_t *soff = sample_offsets + run.p0; // np + 1 values; sample 0 of the run at soff[0]
+        const int64_t S = soff[np] - soff[0];
+        if (S == 0) {
+            if (norm_scale)
+                for (int k = 0; k < np; ++k)
+                    norm_scale[run.p0 + k] = make_problem(pair_input(run.p0 + k), opts, cfg).norm_scale;
+            continue;
+        }
+        // ---- problems, packed upload, pair records (as refine_batch / select_batch) ----
+        Clock::time_point t0 = Clock::now();
+        std::vector<double> norm(np);
+        std::vector<PairData> Dh(np);
+        std::vector<PairConst> Ch(np);
+        std::vector<int64_t> off(np);
+        std::vector<double> stage(6 * (size_t)T);
+        DevArray<double> d_data((size_t)kRefineRows * T);
+        for (int k = 0; k < np; ++k) {
+            const int32_t p = run.p0 + k;
+            const int64_t n = offsets[p + 1] - offsets[p];
+            const Problem P = make_problem(pair_input(p), opts, cfg);
+            off[k] = offsets[p] - offsets[run.p0];
+            refine_pack_pair(P.H.x0.data(), P.H.x1.data(), P.H.d0.data(), P.H.d1.data(), n, off[k], stage.data());
+            const double *rows[kRefineRows];
+            for (int r = 0; r < kRefineRows; ++r) rows[r] = d_data.p + refine_row(T, off[k], n, r);
+            PairData &D = Dh[k];
+            D.x0u = rows[0];
+            D.x0v = rows[1];
+            D.x1u = rows[2];
+            D.x1v = rows[3];
+            D.d0 = rows[4];
+            D.d1 = rows[5];
+            D.r0 = rows[6];
+            D.r1 = rows[7];
+            D.a0 = rows[8];
+            D.a1 = rows[9];
+            D.b0 = rows[10];
+            D.b1 = rows[11];
+            Ch[k] = P.C;
+            norm[k] = P.norm_scale;
+            if (norm_scale) norm_scale[p] = P.norm_scale;
+        }
+        DevArray<PairData> d_D(np);
+        DevArray<PairConst> d_C(np);
+        if (T > 0)
+            MP_HIP(hipMemcpyAsync(d_data.p, stage.data(), sizeof(double) * 6 * (size_t)T, hipMemcpyHostToDevice,
+                                  stream));
+        MP_HIP(hipMemcpyAsync(d_D.p, Dh.data(), sizeof(PairData) * np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_C.p, Ch.data(), sizeof(PairConst) * np, hipMemcpyHostToDevice, stream));
+        if (v == kCal)
+            for (int k = 0; k < np; ++k) {
+                double *base = d_data.p;
+                const int64_t n = Ch[k].n;
+                auto row = [&](int r) { return base + refine_row(T, off[k], n, r); };
+                MP_HIP(launch_prep_pair(stream, Ch[k], Dh[k], row(6), row(7), row(8), row(9), row(10), row(11)));
+            }
+        stage_end(t0, tm.pairs_ms);
+
+        // ---- the samples, slab by slab ----
+        for (const HypSlab &s : hyp_slabs(S, sample_chunk)) {
+            const int64_t ns = s.s1 - s.s0;
+            const int64_t g0 = soff[0] + s.s0; // the slab's first sample in the caller's arrays
+            t0 = Clock::now();
+            hyp_items(np, soff, sample_types + soff[0], s, cap, plan);
+            const size_t nl[2] = {plan.list[0].size(), plan.list[1].size()};
+            const size_t ni[2] = {plan.items[0].size(), plan.items[1].size()};
+            if ((int64_t)(nl[0] + nl[1]) != ns || (int64_t)(ni[0] + ni[1]) > ns)
+                throw std::logic_error("hypothesize_batch: the slab's lists do not cover its samples");
+            // (only the slots a solver reads, range-checked above, reach the device)
+            for (int64_t b = 0; b < ns; ++b) {
+                const int k = ksz[sample_types[g0 + b] != 0 ? 1 : 0];
+                const int32_t *q = sample_idx + kSampleStride * (g0 + b);
+                int *o = h_samples.data() + kSampleStride * b;
+                for (int a = 0; a < kSampleStride; ++a) o[a] = a < k ? q[a] : 0;
+            }
+            std::copy(plan.list[0].begin(), plan.list[0].end(), h_list.begin());
+            std::copy(plan.list[1].begin(), plan.list[1].end(), h_list.begin() + nl[0]);
+            std::copy(plan.items[0].begin(), plan.items[0].end(), h_items.begin());
+            std::copy(plan.items[1].begin(), plan.items[1].end(), h_items.begin() + ni[0]);
+            if (timed) tm.plan_ms += 1e3 * secs(t0);
+            t0 = Clock::now();
+            MP_HIP(hipMemcpyAsync(d_samples.p, h_samples.data(), sizeof(int) * kSampleStride * (size_t)ns,
+                                  hipMemcpyHostToDevice, stream));
+            MP_HIP(hipMemcpyAsync(d_list.p, h_list.data(), sizeof(int) * (size_t)ns, hipMemcpyHostToDevice, stream));
+            MP_HIP(hipMemcpyAsync(d_items.p, h_items.data(), sizeof(HypItem) * (ni[0] + ni[1]), hipMemcpyHostToDevice,
+                                  stream));
+            MP_HIP(hipMemsetAsync(d_models.p, 0, sizeof(Model) * (size_t)ns * maxm, stream));
+            MP_HIP(hipMemsetAsync(d_counts.p, 0, sizeof(int) * (size_t)ns, stream));
+            stage_end(t0, tm.upload_ms);
+            t0 = Clock::now();
+            MP_HIP(launch_hyp_solve(stream, v, d_D.p, d_C.p, d_items.p, (int)ni[0], d_list.p, d_items.p + ni[0],
+                                    (int)ni[1], d_list.p + nl[0], (int)nl[1], d_samples.p, W, d_models.p, d_counts.p));
+            stage_end(t0, tm.solve_ms);
+            t0 = Clock::now();
+            Model *out = models + (size_t)g0 * maxm;
+            MP_HIP(hipMemcpyAsync(out, d_models.p, sizeof(Model) * (size_t)ns * maxm, hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipMemcpyAsync(counts + g0, d_counts.p, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, stream));
+            // (the host buffers are rewritten for the next slab, the device ones by its launches)
+            MP_HIP(hipStreamSynchronize(stream));
+            // user units: the focals times the pair's normalisation scale (one product each)
+            if (v != kCal) {
+                int k = (int)(std::upper_bound(soff, soff + np + 1, g0) - soff) - 1;
+                for (int64_t b = 0; b < ns; ++b) {
+                    while (soff[k + 1] <= g0 + b) ++k;
+                    const int cnt = counts[g0 + b];
+                    if (cnt < 0 || cnt > maxm) throw std::runtime_error("hypothesize_batch: model count out of range");
+                    for (int j = 0; j < cnt; ++j) {
+                        Model &m = out[(size_t)b * maxm + j];
+                        m.focal0 *= norm[k];
+                        m.focal1 *= norm[k];
+                    }
+                }
+            }
+            if (timed) tm.download_ms += 1e3 * secs(t0);
+        }
+    }
+    if (timed) {
+        std::lock_guard<std::mutex> lk(g_hyp_mu);
+        g_hyp_timing = tm;
     }
 }
 

@@ -151,6 +151,36 @@ struct SelectTiming {
 int select_tile_override(int tile);
 SelectTiming select_timing_last();
 
+// The estimators' sample models over many pairs (mp_hypothesize_batch).  Pairs laid out as
+// refine_batch's; pair p's samples are sample_offsets[p] .. sample_offsets[p + 1] - 1 of
+// sample_types (0 the MD solver, 1 the point solver) and sample_idx (8 slots per sample,
+// indices within the pair; the first 3 / 4 read for type 0, the first 5 / 6 / 7 for type 1).
+// Sample s: counts[s] models at models[s * max_models(variant) ..], the ones the
+// estimator's MinimalSolver stage forms for that pair, solver type and sample (the exact MD
+// solver with the min-depth filter; 5pt / 6pt / 7pt with depth tail, compaction and the
+// shared-focal duplicate rule), in its order and to the bit, in user units (SF / TF: the
+// focals times the pair's norm_scale); slots from counts[s] on are zero.  Supported: the
+// variants 0 .. 2 with use_shift on and without use_ours / use_4p4d.  Runs of `chunk` pairs
+// as refine_batch; `sample_chunk` samples (0: host/hypothesis_plan.h's default) are on the
+// device at once.  Results depend on neither, nor on the other samples of the call.
+// norm_scale (nullable): one per pair.  All arguments are checked before any device call.
+void hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                       const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                       const double *cam1, const RansacOptions &opts, const EstimatorConfig &cfg,
+                       const int64_t *sample_offsets, const int32_t *sample_types, const int32_t *sample_idx,
+                       Model *models, int32_t *counts, double *norm_scale, int64_t chunk, int64_t sample_chunk,
+                       int device);
+// Measurement hook (mp_debug_hypothesize_timing): the stage times of the last call made
+// while profiling was enabled (profile_enable), every stage waited for.
+struct HypTiming {
+    double pairs_ms = 0;    // make_problem, the packed upload, the pair preparation
+    double plan_ms = 0;     // host: lists, work items and the checked sample copy of every slab
+    double upload_ms = 0;   // samples, lists and items to the device, the output's zeroing
+    double solve_ms = 0;    // the solve launches
+    double download_ms = 0; // models and counts back, the focals to user units
+};
+HypTiming hypothesize_timing_last();
+
 // Standalone solvers on the device (mp_solve_* / mp_relpose_5pt).
 // alt: 0 default MD solver, 1 use_ours, 2 use_4p4d (two-focal)
 int solve_md_direct(int variant, const double *x, const double *y, const double *dx, const double *dy, double *sols,

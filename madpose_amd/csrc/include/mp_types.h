@@ -152,6 +152,13 @@ struct SelectBest {
     int index, pad;
 };
 
+// One workgroup of the multi-pair solve stages (kernels/hypothesize_batch.h; planned by
+// host/hypothesis_plan.h): `count` samples of one solver type of pair `pair` (of the run),
+// entries first .. first + count - 1 of the slab's list of that type.
+struct HypItem {
+    int pair, first, count, pad;
+};
+
 constexpr int kMaxModelsCal = 10; // MD <= 4, 5pt <= 10
 constexpr int kMaxModelsSF = 16;  // MD <= 8, 6pt <= 15
 constexpr int kMaxModelsTF = 4;   // MD <= 4, 7pt <= 3

@@ -66,11 +66,13 @@ __device__ unsigned long long e6_prof[8];
 // latter's register allocation is not set by this register-heavy part.
 constexpr int kPenStride = 300;
 static_assert(kPenStride == kPtPenStride, "the engine sizes the pencil workspace with kPtPenStride (kernels.h)");
-__global__ void __launch_bounds__(64) pt_pencil6_kernel(PairData D, const int *list, int nlist, const int *samples,
-                                                        double *cand, int cand_stride, double *pen) {
+// (the body of workgroup `bid`: pt_pencil6_kernel, and the multi-pair form of
+// hypothesize_batch.h)
+__device__ __forceinline__ void pt_pencil6_body(int bid, const PairData &D, const int *list, int nlist,
+                                                const int *samples, double *cand, int cand_stride, double *pen) {
     __shared__ double shN[kGrpPerWg][27];
     const int g = threadIdx.x / kGrp, r = threadIdx.x % kGrp;
-    const int idx = blockIdx.x * kGrpPerWg + g;
+    const int idx = bid * kGrpPerWg + g;
     const bool active = idx < nlist;
     const int *smp = samples + (size_t)list[active ? idx : nlist - 1] * kSampleStride;
     {
@@ -111,6 +113,11 @@ __global__ void __launch_bounds__(64) pt_pencil6_kernel(PairData D, const int *l
             P[200 + 10 * r + c] = m2[c];
         }
     }
+}
+
+__global__ void __launch_bounds__(64) pt_pencil6_kernel(PairData D, const int *list, int nlist, const int *samples,
+                                                        double *cand, int cand_stride, double *pen) {
+    pt_pencil6_body(blockIdx.x, D, list, nlist, samples, cand, cand_stride, pen);
 }
 
 // (EISPACK sign transfer, used by the generated QR of eig15_gen.h)

@@ -52,15 +52,17 @@ __device__ inline double gsum8_ordered(double v) {
 // sample), subgroup c tests candidate c (one DLT triangulation per lane instead of
 // four), the four good-point counts are exchanged across the subgroups, and the
 // subgroups then run the depth fit redundantly (subgroup 0 writes).
+// (the body of workgroup `bid`: pt_tail7_group_kernel, and the multi-pair form of
+// hypothesize_batch.h)
 template <int G>
-__global__ void __launch_bounds__(64) pt_tail7_group_kernel(PairData D, PairConst C, const int *list, int nlist,
-                                                            const double *cand, const int *ncand, const int *samples,
-                                                            Model *slots, int *valid) {
+__device__ __forceinline__ void pt_tail7_group_body(int bid, const PairData &D, const PairConst &C, const int *list,
+                                                    int nlist, const double *cand, const int *ncand,
+                                                    const int *samples, Model *slots, int *valid) {
     static_assert(G == 8 || G == 32, "8 or 32 lanes per (root, sample)");
     constexpr int K = 7;
     const int lane = threadIdx.x % kTail;
     const int sub = (threadIdx.x % G) / kTail; // candidate of this subgroup (G = 32)
-    const int gid = (int)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) / G);
+    const int gid = (int)((bid * (size_t)blockDim.x + threadIdx.x) / G);
     const int k = gid / nlist, idx = gid - k * nlist;
     if (k >= 3 || k >= ncand[idx]) return; // the whole group leaves together
     const int *s = samples + (size_t)list[idx] * kSampleStride;
@@ -115,6 +117,13 @@ __global__ void __launch_bounds__(64) pt_tail7_group_kernel(PairData D, PairCons
         if (ok) slots[q] = m;
         valid[q] = ok ? 1 : 0;
     }
+}
+
+template <int G>
+__global__ void __launch_bounds__(64) pt_tail7_group_kernel(PairData D, PairConst C, const int *list, int nlist,
+                                                            const double *cand, const int *ncand, const int *samples,
+                                                            Model *slots, int *valid) {
+    pt_tail7_group_body<G>(blockIdx.x, D, C, list, nlist, cand, ncand, samples, slots, valid);
 }
 
 // Calibrated tail (src/hybrid_pose_estimator.cpp:134-182) with one 8-lane group per
@@ -208,13 +217,15 @@ __device__ inline int gsum16(int v) {
     return v + dpp_i<dpp::kMirror>(v);
 }
 
-__global__ void __launch_bounds__(64) pt_tail6_group_kernel(PairData D, PairConst C, const int *list, int nlist,
-                                                            const double *cand, const int *ncand, const int *samples,
-                                                            Model *slots, int *valid) {
+// (the body of workgroup `bid`: pt_tail6_group_kernel, and the multi-pair form of
+// hypothesize_batch.h)
+__device__ __forceinline__ void pt_tail6_group_body(int bid, const PairData &D, const PairConst &C, const int *list,
+                                                    int nlist, const double *cand, const int *ncand,
+                                                    const int *samples, Model *slots, int *valid) {
     constexpr int K = 6, kRoots = 15, kPoses = 2;
     __shared__ Tail6Shared sh;
     const int g = threadIdx.x / kGrp, r = threadIdx.x % kGrp;
-    const int gid = (int)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) / kGrp);
+    const int gid = (int)((bid * (size_t)blockDim.x + threadIdx.x) / kGrp);
     const int k = gid / nlist, idx = gid - k * nlist;
     if (k >= kRoots || k >= ncand[idx]) return; // the whole group leaves together
     const double *cd = cand + (size_t)idx * kPtCandStride;
@@ -402,6 +413,12 @@ __global__ void __launch_bounds__(64) pt_tail6_group_kernel(PairData D, PairCons
             valid[q] = okm ? 1 : 0;
         }
     }
+}
+
+__global__ void __launch_bounds__(64) pt_tail6_group_kernel(PairData D, PairConst C, const int *list, int nlist,
+                                                            const double *cand, const int *ncand, const int *samples,
+                                                            Model *slots, int *valid) {
+    pt_tail6_group_body(blockIdx.x, D, C, list, nlist, cand, ncand, samples, slots, valid);
 }
 
 } // namespace

@@ -144,6 +144,20 @@ hipError_t launch_select_score(hipStream_t s, int variant, int tile, const PairD
 // out[k] = GetBestEstimatedModelId's walk over scores[moff[k] .. moff[k + 1]) (np pairs)
 hipError_t launch_select_argmin(hipStream_t s, const int64_t *moff, int np, const double *scores, SelectBest *out);
 
+// The estimator's solve stages over explicit samples of the resident pairs
+// (hypothesize_batch.h; mp_hypothesize_batch).  samples: the slab's sample indices
+// (kSampleStride per slab position); md_list / pt_list: the slab positions of the two
+// solver types, cut into the work items md_items / pt_items (host/hypothesis_plan.h); npt:
+// the length of pt_list.  Sample at slab position b: its models to models[b * max_models
+// ..] in the estimator's order, their number to counts[b]; slots past it are not written.
+// W: cand / ncand / slots / valid / pen sized for npt point samples (md_ws unused).  The
+// launch count does not depend on the number of pairs: 1 for the MD samples, 3 (calibrated,
+// two focal) or 5 (shared focal) for the point samples.
+hipError_t launch_hyp_solve(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                            const HypItem *md_items, int nmd_items, const int *md_list, const HypItem *pt_items,
+                            int npt_items, const int *pt_list, int npt, const int *samples, const PtWorkspace &W,
+                            Model *models, int *counts);
+
 // squared Bougnoux focals of k fundamental matrices (9 doubles each) into out (2 each)
 hipError_t launch_bougnoux(hipStream_t s, const double *F, int64_t k, double *out);
 

@@ -137,12 +137,17 @@ __device__ inline bool md_accept(const PairConst &C, Model &m) {
     return false;
 }
 
+// (REC false: the model alone -- the multi-pair solve stages of hypothesize_batch.h, whose
+// callers prepare score records on the host)
+template <bool REC = true>
 __device__ inline void put_model(const PairConst &C, const Model &m, int b, int slot, int maxm, Model *models,
                                  ScoreRec *recs) {
     models[(size_t)b * maxm + slot] = m;
-    ScoreRec r;
-    prepare_score_rec(C, m, r);
-    recs[(size_t)b * maxm + slot] = r;
+    if constexpr (REC) {
+        ScoreRec r;
+        prepare_score_rec(C, m, r);
+        recs[(size_t)b * maxm + slot] = r;
+    }
 }
 
 // ALT: instantiated with the option-gated alternate solvers (use_ours / use_4p4d);
@@ -275,7 +280,7 @@ __device__ __forceinline__ void md_sample_inputs(const PairData &D, const PairCo
 }
 
 // the body of workgroup `bid` (md_exact_kernel, and the fused MD + 5pt launch below)
-template <int V, int R>
+template <int V, int R, bool REC = true>
 __device__ __forceinline__ void md_exact_body(int bid, const PairData &D, const PairConst &C, const int *list,
                                               int nlist, const int *samples, Model *models, ScoreRec *recs,
                                               int *counts, int maxm) {
@@ -302,7 +307,7 @@ __device__ __forceinline__ void md_exact_body(int bid, const PairData &D, const 
         mdx_sols<Sys>(LaneScratch{scr + threadIdx.x, 64}, x, y, dx, dy, [&](const double (&sol)[6]) {
             Model m;
             if (accept(sol, m)) {
-                if (n < maxm) put_model(C, m, b, n, maxm, models, recs);
+                if (n < maxm) put_model<REC>(C, m, b, n, maxm, models, recs);
                 ++n;
             }
         });
@@ -343,7 +348,7 @@ __device__ __forceinline__ void md_exact_body(int bid, const PairData &D, const 
             const int pos = n + __popcll(mine & ((1ull << r) - 1));
             if (keep && pos < maxm) {
                 mdx::procrustes<K>(X, Y, m);
-                put_model(C, m, b, pos, maxm, models, recs);
+                put_model<REC>(C, m, b, pos, maxm, models, recs);
             }
             n += __popcll(mine);
             if (!__any(active && (j + 1) * R < nr)) break; // (uniform) no sample of the wave has more roots
@@ -566,9 +571,11 @@ template <> struct PtTraits<kTF> {
 // two-focal root stage, one lane per sample: the 7-point fundamental matrices
 // (PoseLib relpose_7pt: cubic by multilinear expansion, closed-form roots; the
 // oracle's relpose_7pt operation for operation, oracle/src/pt_poselib.cpp)
-__global__ void __launch_bounds__(64) pt_roots7_kernel(PairData D, const int *list, int nlist, const int *samples,
-                                                       double *cand, int *ncand) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+// (the body of workgroup `bid`: pt_roots7_kernel, and the multi-pair form of
+// hypothesize_batch.h)
+__device__ __forceinline__ void pt_roots7_body(int bid, const PairData &D, const int *list, int nlist,
+                                               const int *samples, double *cand, int *ncand) {
+    const int idx = bid * blockDim.x + threadIdx.x;
     if (idx >= nlist) return;
     const int *s = samples + (size_t)list[idx] * kSampleStride;
     double *out = cand + (size_t)idx * kCandStride;
@@ -585,6 +592,11 @@ __global__ void __launch_bounds__(64) pt_roots7_kernel(PairData D, const int *li
     ncand[idx] = n;
 }
 
+__global__ void __launch_bounds__(64) pt_roots7_kernel(PairData D, const int *list, int nlist, const int *samples,
+                                                       double *cand, int *ncand) {
+    pt_roots7_body(blockIdx.x, D, list, nlist, samples, cand, ncand);
+}
+
 // Compaction of a point sample's valid tail slots into its model slots, in slot
 // order: one lane per slot (G lanes per sample, G >= the slot count), the kept
 // slot's position from a ballot over the group, so the models' score records are
@@ -592,15 +604,17 @@ __global__ void __launch_bounds__(64) pt_roots7_kernel(PairData D, const int *li
 // roots of the interpolated q(u) that the polish took to the same solution give the
 // same pose twice; a slot equal to an earlier valid one is dropped (the first stays).
 // At most maxm models are kept (the first ones).
-template <int V>
-__global__ void __launch_bounds__(64) pt_compact_kernel(PairConst C, const int *list, int nlist, const int *ncand,
-                                                        const Model *slots, const int *valid, Model *models,
-                                                        ScoreRec *recs, int *counts, int maxm) {
+// (the body of workgroup `bid`: pt_compact_kernel, and the multi-pair form of
+// hypothesize_batch.h, which writes no score records)
+template <int V, bool REC = true>
+__device__ __forceinline__ void pt_compact_body(int bid, const PairConst &C, const int *list, int nlist,
+                                                const int *ncand, const Model *slots, const int *valid, Model *models,
+                                                ScoreRec *recs, int *counts, int maxm) {
     using T = PtTraits<V>;
     constexpr int kSlots = T::kPosesPerRoot * T::kRoots;
     constexpr int G = kSlots <= 4 ? 4 : 32;
     static_assert(kSlots <= G && kSlots <= kSlotStride && 64 % G == 0, "slot group");
-    const int gid = (int)((blockIdx.x * (size_t)blockDim.x + threadIdx.x) / G), q = threadIdx.x % G;
+    const int gid = (int)((bid * (size_t)blockDim.x + threadIdx.x) / G), q = threadIdx.x % G;
     const bool active = gid < nlist;
     const int idx = active ? gid : nlist - 1;
     const int total = T::kPosesPerRoot * min(ncand[idx], T::kRoots);
@@ -621,11 +635,18 @@ __global__ void __launch_bounds__(64) pt_compact_kernel(PairConst C, const int *
     const int lane = threadIdx.x & 63, g0 = lane & ~(G - 1);
     const unsigned long long mine = (ball >> g0) & (G == 64 ? ~0ull : ((1ull << G) - 1));
     const int pos = __popcll(mine & ((1ull << q) - 1));
-    if (keep && pos < maxm) put_model(C, slots[base + q], list[idx], pos, maxm, models, recs);
+    if (keep && pos < maxm) put_model<REC>(C, slots[base + q], list[idx], pos, maxm, models, recs);
     if (active && q == 0) {
         const int n = __popcll(mine);
         counts[list[idx]] = n < maxm ? n : maxm;
     }
+}
+
+template <int V>
+__global__ void __launch_bounds__(64) pt_compact_kernel(PairConst C, const int *list, int nlist, const int *ncand,
+                                                        const Model *slots, const int *valid, Model *models,
+                                                        ScoreRec *recs, int *counts, int maxm) {
+    pt_compact_body<V>(blockIdx.x, C, list, nlist, ncand, slots, valid, models, recs, counts, maxm);
 }
 
 // FAST: score_type 0 (hybrid, no gating) and not scale-only, and for the calibrated
@@ -1748,3 +1769,5 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 #include "refine_batch.h"
 // ranking of candidate models over many resident pairs (mp_select_batch)
 #include "select_batch.h"
+
+#include "hypothesize_batch.h"
