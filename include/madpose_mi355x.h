@@ -362,6 +362,69 @@ int mp_hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets,
  * for then. */
 int mp_debug_hypothesize_timing(double *out_ms /* 5 */);
 
+/* Pair sets: pairs set up once and resident on one device, for callers who run the stages
+ * mp_hypothesize_batch -> mp_select_batch -> mp_refine_batch (or any of them, several times)
+ * over the same pairs.  Each batch entry sets its pairs up per call (the problem of every
+ * pair, the packed upload, the pair records, the calibrated preparation); a set does it at
+ * creation, and mp_hypothesize_set / mp_select_set / mp_refine_set are the same stages on
+ * the resident pairs.
+ * mp_pair_set_create: pair layout exactly as mp_refine_batch (offsets, min_depth 2 per pair,
+ * cameras 9 or 2 per pair).  The thresholds, weights, score type, min_depth, use_shift and
+ * the MD alternates live in the per-pair device records, so options and config belong to
+ * the set, not to a call (copies are kept for the LM).  All pairs are one resident range on
+ * `device`: at most MP_PAIR_SET_MAX_CORRESPONDENCES correspondences.  MP_EINVAL, checked
+ * before any array but offsets is read and before the device is touched: a bad variant, a
+ * negative count, null required pointers, negative or decreasing offsets, a pair above 2^28
+ * or a total above the bound, invalid options.  num_pairs == 0 gives a valid empty set (no
+ * device call).  mp_pair_set_destroy(NULL) is MP_OK.  Sets still open when the process ends
+ * are released at library teardown.
+ * mp_pair_set_info (every output nullable): resident_bytes = 96 per correspondence for the
+ * rows, plus 12 per correspondence for each list buffer allocated so far -- none after
+ * creation or mp_hypothesize_set, one after mp_select_set, two after mp_refine_set (120 per
+ * correspondence then); the per-pair records (under 1 KiB a pair) are not counted.
+ * Calls: pair_ids NULL = all pairs in order, num_sel must equal the set's pair count;
+ * otherwise num_sel indices into the set in any order, each in range and at most once
+ * (MP_EINVAL names the position).  Every per-pair argument and result is indexed by the
+ * position j in the selection: models[j] / results[j], model_offsets / sample_offsets
+ * (num_sel + 1 values) and what they index; inlier_idx (nullable) is the batch layout over
+ * the selected pairs in selection order: entry j at 3 * (correspondences of the entries
+ * before j), list t at + t * n_j.  Each call returns exactly the bytes its batch entry
+ * returns on the selected pairs' inputs in that order with the set's options and config
+ * (mp_select_batch takes no min_depth: no score depends on it).  mp_hypothesize_set gives
+ * MP_EINVAL on a set whose variant or options mp_hypothesize_batch rejects (MP_SCALE_ONLY,
+ * use_shift = 0, use_ours, use_4p4d); such a set can be selected on and refined.  The
+ * normalization scales are mp_pair_set_norm_scales (one per pair of the set).
+ * A call leaves nothing in the set that a later call can see: any order of calls gives
+ * each call the bytes it gives on a fresh set.  Calls on one set are serialised; calls on
+ * different sets are independent. */
+typedef struct mp_pair_set mp_pair_set;
+#define MP_PAIR_SET_MAX_CORRESPONDENCES 67108864 /* 2^26; 120 bytes resident each */
+int mp_pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                       const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                       const double *cam1, const mp_ransac_options *options, const mp_estimator_config *config,
+                       int device, mp_pair_set **out);
+int mp_pair_set_destroy(mp_pair_set *set);
+int mp_pair_set_info(const mp_pair_set *set, int32_t *variant, int32_t *num_pairs, int64_t *correspondences,
+                     int64_t *resident_bytes, int32_t *device);
+int mp_pair_set_norm_scales(const mp_pair_set *set, double *out /* num_pairs */);
+int mp_refine_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int rounds,
+                  mp_model *models /* in/out, one per selected pair */, mp_refine_result *results,
+                  int32_t *inlier_idx /* nullable */);
+int mp_select_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
+                  const mp_model *models, double *scores /* nullable */, int32_t *counts /* nullable */,
+                  mp_select_result *results, int32_t *inlier_idx /* nullable */, int64_t model_chunk);
+int mp_hypothesize_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                       const int32_t *sample_types, const int32_t *sample_idx, mp_model *models, int32_t *counts,
+                       int64_t sample_chunk);
+/* Test and measurement hooks.  mp_debug_pair_set_prep: how the pair setups that follow (of
+ * sets and of the batch entries; process-wide) derive the calibrated rows -- 0: one launch
+ * over all pairs, 1: one launch per pair, the form before; the rows are equal bit for bit.
+ * MP_EINVAL for another mode.  mp_debug_pair_set_rows: the twelve device rows of one pair
+ * (x0u x0v x1u x1v d0 d1 r0 r1 a0 a1 b0 b1, n doubles each; rows 6 .. 11 are written for
+ * calibrated and scale-only sets only). */
+int mp_debug_pair_set_prep(int mode);
+int mp_debug_pair_set_rows(const mp_pair_set *set, int32_t pair, double *out /* 12 n */);
+
 /* bougnoux_focals (src/hybrid_pose_two_focal_estimator.cpp:11-32; numpy twin
  * madpose/utils.py:25-56 bougnoux_numpy with p1 = p2 = 0): squared focal lengths
  * (f0^2, f1^2) of k fundamental matrices F (k x 9, row-major) into out (k x 2), on

@@ -14,6 +14,7 @@ from .api import (  # noqa: F401
     HybridLORansacOptions,
     HybridRansacStatistics,
     LORansacOptions,
+    PairSet,
     PoseAndScale,
     PoseScaleOffset,
     PoseScaleOffsetSharedFocal,

@@ -160,6 +160,22 @@ EXPORTS = {
                                             c_int64_p, c_int32_p, c_int32_p, ctypes.POINTER(mp_model), c_int32_p,
                                             c_double_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int]),
     "mp_debug_hypothesize_timing": (ctypes.c_int, [c_double_p]),
+    "mp_pair_set_create": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, c_double_p,
+                                          ctypes.POINTER(mp_ransac_options), ctypes.POINTER(mp_estimator_config),
+                                          ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "mp_pair_set_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "mp_pair_set_info": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, c_int32_p, c_int64_p, c_int64_p, c_int32_p]),
+    "mp_pair_set_norm_scales": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),
+    "mp_refine_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int,
+                                     ctypes.POINTER(mp_model), ctypes.POINTER(mp_refine_result), c_int32_p]),
+    "mp_select_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, c_int64_p, ctypes.POINTER(mp_model),
+                                     c_double_p, c_int32_p, ctypes.POINTER(mp_select_result), c_int32_p,
+                                     ctypes.c_int64]),
+    "mp_hypothesize_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, c_int64_p, c_int32_p, c_int32_p,
+                                          ctypes.POINTER(mp_model), c_int32_p, ctypes.c_int64]),
+    "mp_debug_pair_set_prep": (ctypes.c_int, [ctypes.c_int]),
+    "mp_debug_pair_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p]),
     "mp_debug_select_tile": (ctypes.c_int, [ctypes.c_int]),
     "mp_debug_select_timing": (ctypes.c_int, [c_double_p]),
     "mp_refine_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,

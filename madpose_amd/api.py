@@ -415,6 +415,147 @@ def estimate_batch(variant, pairs, options, est_config=None, device=None, num_st
     return out
 
 
+def _concat_pairs(variant, pairs, with_min_depth=True):
+    """The pairs of a batch call or a PairSet as the C ABI takes them: (offs, X0, X1, D0, D1,
+    MD, C0, C1) -- offs a list of len(pairs) + 1 offsets, the rest contiguous float64 arrays
+    (MD None without min_depth).  pairs must not be empty."""
+    ncam = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
+    k0, k1 = ("K0", "K1") if ncam == 9 else ("pp0", "pp1")
+    x0s, x1s, d0s, d1s, mds, c0s, c1s, offs = [], [], [], [], [], [], [], [0]
+    for p in pairs:
+        x0 = _pts(p["x0"], "x0")
+        n = x0.shape[0]
+        x1 = _pts(p["x1"], "x1")
+        if x1.shape[0] != n:
+            raise ValueError("x0 and x1 must have the same number of rows")
+        x0s.append(x0.reshape(-1))
+        x1s.append(x1.reshape(-1))
+        d0s.append(_vec(p["depth0"], n, "depth0"))
+        d1s.append(_vec(p["depth1"], n, "depth1"))
+        if with_min_depth:
+            mds.append(np.asarray(p.get("min_depth", (0.0, 0.0)), dtype=np.float64).reshape(2))
+        c0s.append(np.asarray(p[k0], dtype=np.float64).reshape(ncam))
+        c1s.append(np.asarray(p[k1], dtype=np.float64).reshape(ncam))
+        offs.append(offs[-1] + n)
+    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
+    X0, X1, D0, D1, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, c0s, c1s))
+    MD = cat(mds) if with_min_depth else None
+    if offs[-1] == 0:  # (no correspondence at all: the arrays still need an address)
+        X0, X1, D0, D1 = np.zeros(2), np.zeros(2), np.zeros(1), np.zeros(1)
+    return offs, X0, X1, D0, D1, MD, C0, C1
+
+
+def _refine_results(variant, arr, res, idx, offs):
+    """mp_refine_batch's / mp_refine_set's outputs as RefineResults (offs: the entries'
+    offsets in idx)."""
+    out = []
+    for p in range(len(offs) - 1):
+        n = offs[p + 1] - offs[p]
+        r = RefineResult()
+        r.model = _model_from_c(arr[p], variant)
+        r.score_initial, r.score_final = float(res[p].score_initial), float(res[p].score_final)
+        r.rounds_run, r.rounds_accepted = int(res[p].rounds_run), int(res[p].rounds_accepted)
+        r.status = int(res[p].lm_status)
+        base = 3 * offs[p]
+        r.inlier_indices = [idx[base + t * n: base + t * n + res[p].num_inliers[t]].copy() for t in range(3)]
+        r.norm_scale = float(res[p].norm_scale)
+        out.append(r)
+    return out
+
+
+def _concat_candidates(variant, candidates):
+    """select's candidates as the C ABI takes them: (moffs, arr, keep) -- moffs a list of
+    len(candidates) + 1 offsets, arr the mp_model pointer or array, keep what must stay
+    alive while arr is used."""
+    moffs = [0]
+    for cands in candidates:
+        if isinstance(cands, np.ndarray):
+            if cands.dtype != np.float64 or cands.ndim != 2 or cands.shape[1] != 17:
+                raise ValueError(f"array candidates must be float64 of shape (K, 17), got {cands.dtype} {cands.shape}")
+        moffs.append(moffs[-1] + len(cands))
+    M = moffs[-1]
+    if any(isinstance(cands, np.ndarray) for cands in candidates):
+        # (rows copied as they are; objects through _model_to_c, the same bytes as below)
+        rows = np.zeros((max(M, 1), 17))
+        for p, cands in enumerate(candidates):
+            if isinstance(cands, np.ndarray):
+                rows[moffs[p]:moffs[p + 1]] = cands
+            else:
+                for j, m in enumerate(cands):
+                    c_m = _model_to_c(m, variant)
+                    ctypes.memmove(rows[moffs[p] + j].ctypes.data, ctypes.byref(c_m), ctypes.sizeof(c_m))
+        return moffs, rows.ctypes.data_as(ctypes.POINTER(L.mp_model)), rows
+    arr = (L.mp_model * max(M, 1))(*[_model_to_c(m, variant) for cands in candidates for m in cands])
+    return moffs, arr, arr
+
+
+def _select_results(variant, candidates, res, idx, offs, moffs, scores, counts):
+    """mp_select_batch's / mp_select_set's outputs as SelectResults (scores, counts: the
+    arrays or None)."""
+    out = []
+    for p in range(len(offs) - 1):
+        n = offs[p + 1] - offs[p]
+        r = SelectResult()
+        r.index = int(res[p].best_index)
+        if r.index >= 0 and isinstance(candidates[p], np.ndarray):
+            r.model = _pose_from_row(candidates[p][r.index], variant)
+        else:
+            r.model = candidates[p][r.index] if r.index >= 0 else None
+        r.score = float(res[p].best_score)
+        base = 3 * offs[p]
+        r.inlier_indices = [idx[base + t * n: base + t * n + res[p].num_inliers[t]].copy() for t in range(3)]
+        r.norm_scale = float(res[p].norm_scale)
+        if scores is not None:
+            r.scores = scores[moffs[p]:moffs[p + 1]].copy()
+        if counts is not None:
+            r.counts = counts[3 * moffs[p]:3 * moffs[p + 1]].reshape(-1, 3).copy()
+        out.append(r)
+    return out
+
+
+def _concat_samples(variant, sizes, samples):
+    """hypothesize's samples as the C ABI takes them, checked: (soffs, T, I) -- sizes: the
+    correspondences of each entry's pair."""
+    stride = L.HYPOTHESIZE_SAMPLE_STRIDE
+    ksz = (3 if variant == L.CALIBRATED else 4, (5, 6, 7)[variant])
+    soffs, tys, ids = [0], [], []
+    for p, (n, smp) in enumerate(zip(sizes, samples)):
+        try:
+            types, idx = smp
+        except (TypeError, ValueError):
+            raise ValueError(f"pair {p}: samples must hold one (types, idx) per pair") from None
+        types, idx = np.asarray(types), np.asarray(idx)
+        if types.dtype != np.int32 or idx.dtype != np.int32:
+            raise ValueError(f"pair {p}: types and idx must be int32 arrays")
+        K = types.shape[0] if types.ndim == 1 else -1
+        if K < 0 or idx.shape != (K, stride):
+            raise ValueError(f"pair {p}: types must have shape (K,) and idx (K, {stride}), got {types.shape} "
+                             f"and {idx.shape}")
+        if K:
+            if ((types != 0) & (types != 1)).any():
+                raise ValueError(f"pair {p}: a sample's type must be 0 (MD solver) or 1 (point solver)")
+            for t in (0, 1):
+                rows = idx[types == t][:, :ksz[t]]
+                if rows.shape[0] == 0:
+                    continue
+                if n < ksz[t]:
+                    raise ValueError(f"pair {p}: {n} correspondences are too few for a type-{t} sample")
+                if (rows < 0).any() or (rows >= n).any():
+                    raise ValueError(f"pair {p}: a sample index lies outside [0, {n})")
+                srt = np.sort(rows, axis=1)
+                if (srt[:, 1:] == srt[:, :-1]).any():
+                    raise ValueError(f"pair {p}: a sample repeats an index")
+        tys.append(types)
+        ids.append(idx.reshape(-1))
+        soffs.append(soffs[-1] + K)
+    S = soffs[-1]
+    if S > L.HYPOTHESIZE_MAX_SAMPLES:
+        raise ValueError(f"at most 2^22 samples per call, got {S}")
+    T = np.ascontiguousarray(np.concatenate(tys), dtype=np.int32) if S else np.zeros(1, dtype=np.int32)
+    I = np.ascontiguousarray(np.concatenate(ids), dtype=np.int32) if S else np.zeros(stride, dtype=np.int32)
+    return soffs, T, I
+
+
 class RefineResult:
     """One pair's outcome of refine_batch."""
 
@@ -463,27 +604,7 @@ def refine_batch(variant, pairs, models, options, est_config=None, rounds=1, chu
     P = len(pairs)
     if P == 0:
         return []
-    ncam = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
-    k0, k1 = ("K0", "K1") if ncam == 9 else ("pp0", "pp1")
-    x0s, x1s, d0s, d1s, mds, c0s, c1s, offs = [], [], [], [], [], [], [], [0]
-    for p in pairs:
-        x0 = _pts(p["x0"], "x0")
-        n = x0.shape[0]
-        x1 = _pts(p["x1"], "x1")
-        if x1.shape[0] != n:
-            raise ValueError("x0 and x1 must have the same number of rows")
-        x0s.append(x0.reshape(-1))
-        x1s.append(x1.reshape(-1))
-        d0s.append(_vec(p["depth0"], n, "depth0"))
-        d1s.append(_vec(p["depth1"], n, "depth1"))
-        mds.append(np.asarray(p.get("min_depth", (0.0, 0.0)), dtype=np.float64).reshape(2))
-        c0s.append(np.asarray(p[k0], dtype=np.float64).reshape(ncam))
-        c1s.append(np.asarray(p[k1], dtype=np.float64).reshape(ncam))
-        offs.append(offs[-1] + n)
-    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
-    X0, X1, D0, D1, MD, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, mds, c0s, c1s))
-    if offs[-1] == 0:  # (no correspondence at all: the arrays still need an address)
-        X0, X1, D0, D1 = np.zeros(2), np.zeros(2), np.zeros(1), np.zeros(1)
+    offs, X0, X1, D0, D1, MD, C0, C1 = _concat_pairs(variant, pairs)
     offsets = np.asarray(offs, dtype=np.int64)
     arr = (L.mp_model * P)(*[_model_to_c(m, variant) for m in models])
     res = (L.mp_refine_result * P)()
@@ -492,19 +613,7 @@ def refine_batch(variant, pairs, models, options, est_config=None, rounds=1, chu
                                     _dp(D1), _dp(MD), _dp(C0), _dp(C1), ctypes.byref(o), ctypes.byref(c),
                                     int(rounds), arr, res, idx.ctypes.data_as(L.c_int32_p), int(chunk),
                                     _DEFAULT_DEVICE if device is None else int(device)))
-    out = []
-    for p in range(P):
-        n = offs[p + 1] - offs[p]
-        r = RefineResult()
-        r.model = _model_from_c(arr[p], variant)
-        r.score_initial, r.score_final = float(res[p].score_initial), float(res[p].score_final)
-        r.rounds_run, r.rounds_accepted = int(res[p].rounds_run), int(res[p].rounds_accepted)
-        r.status = int(res[p].lm_status)
-        base = 3 * offs[p]
-        r.inlier_indices = [idx[base + t * n: base + t * n + res[p].num_inliers[t]].copy() for t in range(3)]
-        r.norm_scale = float(res[p].norm_scale)
-        out.append(r)
-    return out
+    return _refine_results(variant, arr, res, idx, offs)
 
 
 class SelectResult:
@@ -557,46 +666,11 @@ def select_batch(variant, pairs, candidates, options, est_config=None, with_scor
     P = len(pairs)
     if P == 0:
         return []
-    ncam = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
-    k0, k1 = ("K0", "K1") if ncam == 9 else ("pp0", "pp1")
-    x0s, x1s, d0s, d1s, c0s, c1s, offs, moffs = [], [], [], [], [], [], [0], [0]
-    for p, cands in zip(pairs, candidates):
-        x0 = _pts(p["x0"], "x0")
-        n = x0.shape[0]
-        x1 = _pts(p["x1"], "x1")
-        if x1.shape[0] != n:
-            raise ValueError("x0 and x1 must have the same number of rows")
-        x0s.append(x0.reshape(-1))
-        x1s.append(x1.reshape(-1))
-        d0s.append(_vec(p["depth0"], n, "depth0"))
-        d1s.append(_vec(p["depth1"], n, "depth1"))
-        c0s.append(np.asarray(p[k0], dtype=np.float64).reshape(ncam))
-        c1s.append(np.asarray(p[k1], dtype=np.float64).reshape(ncam))
-        offs.append(offs[-1] + n)
-        if isinstance(cands, np.ndarray):
-            if cands.dtype != np.float64 or cands.ndim != 2 or cands.shape[1] != 17:
-                raise ValueError(f"array candidates must be float64 of shape (K, 17), got {cands.dtype} {cands.shape}")
-        moffs.append(moffs[-1] + len(cands))
-    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
-    X0, X1, D0, D1, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, c0s, c1s))
-    if offs[-1] == 0:  # (no correspondence at all: the arrays still need an address)
-        X0, X1, D0, D1 = np.zeros(2), np.zeros(2), np.zeros(1), np.zeros(1)
+    offs, X0, X1, D0, D1, _, C0, C1 = _concat_pairs(variant, pairs, with_min_depth=False)
+    moffs, arr, _keep = _concat_candidates(variant, candidates)
     offsets = np.asarray(offs, dtype=np.int64)
     model_offsets = np.asarray(moffs, dtype=np.int64)
     M = moffs[-1]
-    if any(isinstance(cands, np.ndarray) for cands in candidates):
-        # (rows copied as they are; objects through _model_to_c, the same bytes as below)
-        rows = np.zeros((max(M, 1), 17))
-        for p, cands in enumerate(candidates):
-            if isinstance(cands, np.ndarray):
-                rows[moffs[p]:moffs[p + 1]] = cands
-            else:
-                for j, m in enumerate(cands):
-                    c_m = _model_to_c(m, variant)
-                    ctypes.memmove(rows[moffs[p] + j].ctypes.data, ctypes.byref(c_m), ctypes.sizeof(c_m))
-        arr = rows.ctypes.data_as(ctypes.POINTER(L.mp_model))
-    else:
-        arr = (L.mp_model * max(M, 1))(*[_model_to_c(m, variant) for cands in candidates for m in cands])
     res = (L.mp_select_result * P)()
     idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
     scores = np.zeros(max(M, 1), dtype=np.float64) if with_scores else None
@@ -608,25 +682,7 @@ def select_batch(variant, pairs, candidates, options, est_config=None, with_scor
                                     None if counts is None else counts.ctypes.data_as(L.c_int32_p), res,
                                     idx.ctypes.data_as(L.c_int32_p), int(chunk), int(model_chunk),
                                     _DEFAULT_DEVICE if device is None else int(device)))
-    out = []
-    for p in range(P):
-        n = offs[p + 1] - offs[p]
-        r = SelectResult()
-        r.index = int(res[p].best_index)
-        if r.index >= 0 and isinstance(candidates[p], np.ndarray):
-            r.model = _pose_from_row(candidates[p][r.index], variant)
-        else:
-            r.model = candidates[p][r.index] if r.index >= 0 else None
-        r.score = float(res[p].best_score)
-        base = 3 * offs[p]
-        r.inlier_indices = [idx[base + t * n: base + t * n + res[p].num_inliers[t]].copy() for t in range(3)]
-        r.norm_scale = float(res[p].norm_scale)
-        if with_scores:
-            r.scores = scores[moffs[p]:moffs[p + 1]].copy()
-        if with_counts:
-            r.counts = counts[3 * moffs[p]:3 * moffs[p + 1]].reshape(-1, 3).copy()
-        out.append(r)
-    return out
+    return _select_results(variant, candidates, res, idx, offs, moffs, scores, counts)
 
 
 def lm_refine_batch(variant, x0, x1, depth0, depth1, min_depth, cam0, cam1, options, est_config, problems,
@@ -1023,64 +1079,11 @@ def hypothesize_batch(variant, pairs, samples, options, est_config=None, chunk=0
     if P == 0:
         return [], np.zeros(0)
     slots = L.HYPOTHESIZE_SLOTS[variant]
-    stride = L.HYPOTHESIZE_SAMPLE_STRIDE
-    ksz = (3 if variant == L.CALIBRATED else 4, (5, 6, 7)[variant])
-    k0, k1 = ("K0", "K1") if variant == L.CALIBRATED else ("pp0", "pp1")
-    ncam = 9 if variant == L.CALIBRATED else 2
-    x0s, x1s, d0s, d1s, mds, c0s, c1s, offs, soffs, tys, ids = [], [], [], [], [], [], [], [0], [0], [], []
-    for p, (pair, smp) in enumerate(zip(pairs, samples)):
-        x0 = _pts(pair["x0"], "x0")
-        n = x0.shape[0]
-        x1 = _pts(pair["x1"], "x1")
-        if x1.shape[0] != n:
-            raise ValueError("x0 and x1 must have the same number of rows")
-        x0s.append(x0.reshape(-1))
-        x1s.append(x1.reshape(-1))
-        d0s.append(_vec(pair["depth0"], n, "depth0"))
-        d1s.append(_vec(pair["depth1"], n, "depth1"))
-        mds.append(np.asarray(pair.get("min_depth", (0.0, 0.0)), dtype=np.float64).reshape(2))
-        c0s.append(np.asarray(pair[k0], dtype=np.float64).reshape(ncam))
-        c1s.append(np.asarray(pair[k1], dtype=np.float64).reshape(ncam))
-        offs.append(offs[-1] + n)
-        try:
-            types, idx = smp
-        except (TypeError, ValueError):
-            raise ValueError(f"pair {p}: samples must hold one (types, idx) per pair") from None
-        types, idx = np.asarray(types), np.asarray(idx)
-        if types.dtype != np.int32 or idx.dtype != np.int32:
-            raise ValueError(f"pair {p}: types and idx must be int32 arrays")
-        K = types.shape[0] if types.ndim == 1 else -1
-        if K < 0 or idx.shape != (K, stride):
-            raise ValueError(f"pair {p}: types must have shape (K,) and idx (K, {stride}), got {types.shape} "
-                             f"and {idx.shape}")
-        if K:
-            if ((types != 0) & (types != 1)).any():
-                raise ValueError(f"pair {p}: a sample's type must be 0 (MD solver) or 1 (point solver)")
-            for t in (0, 1):
-                rows = idx[types == t][:, :ksz[t]]
-                if rows.shape[0] == 0:
-                    continue
-                if n < ksz[t]:
-                    raise ValueError(f"pair {p}: {n} correspondences are too few for a type-{t} sample")
-                if (rows < 0).any() or (rows >= n).any():
-                    raise ValueError(f"pair {p}: a sample index lies outside [0, {n})")
-                srt = np.sort(rows, axis=1)
-                if (srt[:, 1:] == srt[:, :-1]).any():
-                    raise ValueError(f"pair {p}: a sample repeats an index")
-        tys.append(types)
-        ids.append(idx.reshape(-1))
-        soffs.append(soffs[-1] + K)
+    offs, X0, X1, D0, D1, MD, C0, C1 = _concat_pairs(variant, pairs)
+    soffs, T, I = _concat_samples(variant, [offs[p + 1] - offs[p] for p in range(P)], samples)
     S = soffs[-1]
-    if S > L.HYPOTHESIZE_MAX_SAMPLES:
-        raise ValueError(f"at most 2^22 samples per call, got {S}")
-    cat = lambda xs: np.ascontiguousarray(np.concatenate(xs), dtype=np.float64)
-    X0, X1, D0, D1, MD, C0, C1 = (cat(v) for v in (x0s, x1s, d0s, d1s, mds, c0s, c1s))
-    if offs[-1] == 0:  # (no correspondence at all: the arrays still need an address)
-        X0, X1, D0, D1 = np.zeros(2), np.zeros(2), np.zeros(1), np.zeros(1)
     offsets = np.asarray(offs, dtype=np.int64)
     sample_offsets = np.asarray(soffs, dtype=np.int64)
-    T = np.ascontiguousarray(np.concatenate(tys), dtype=np.int32) if S else np.zeros(1, dtype=np.int32)
-    I = np.ascontiguousarray(np.concatenate(ids), dtype=np.int32) if S else np.zeros(stride, dtype=np.int32)
     models = np.zeros((max(S, 1), slots, 17))
     counts = np.zeros(max(S, 1), dtype=np.int32)
     norm = np.ones(P)
@@ -1093,6 +1096,198 @@ def hypothesize_batch(variant, pairs, samples, options, est_config=None, chunk=0
                                          _DEFAULT_DEVICE if device is None else int(device)))
     out = [(models[soffs[p]:soffs[p + 1]].copy(), counts[soffs[p]:soffs[p + 1]].copy()) for p in range(P)]
     return out, norm
+
+
+class PairSet:
+    """Pairs set up once and resident on the device (mp_pair_set_*): hypothesize, select
+    and refine as methods on them.
+
+    hypothesize_batch, select_batch and refine_batch each set their pairs up per call (the
+    problem of every pair, the packed upload, the pair records, the calibrated preparation);
+    a PairSet does it once.  pairs: estimate_batch's dicts; options and est_config are bound
+    at creation (the thresholds, weights, score type and min depths live in the pairs'
+    device records).  Every method takes pair_ids (None: all pairs in order; else distinct
+    indices into the set in any order) and takes and returns one entry per selected pair, in
+    selection order, with exactly the values the batch function returns for [pairs[i] for i
+    in pair_ids] under the set's options and config.  A call leaves nothing in the set that
+    a later call can see.  Use as a context manager, or close(); any method after close()
+    raises ValueError."""
+
+    def __init__(self, variant, pairs, options, est_config=None, device=None):
+        self._h = None
+        if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL, L.SCALE_ONLY):
+            raise ValueError("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)")
+        if est_config is None:
+            est_config = EstimatorConfig()
+        self.variant = variant
+        self.device = _DEFAULT_DEVICE if device is None else int(device)
+        self._hyp_error = None  # why hypothesize is not available on this set
+        if variant == L.SCALE_ONLY:
+            self._hyp_error = "hypothesize does not support scale only (variant 3)"
+        elif not est_config.use_shift:
+            self._hyp_error = "hypothesize does not support use_shift = False"
+        elif getattr(options, "use_ours", False) or getattr(options, "use_4p4d", False):
+            self._hyp_error = "hypothesize does not support the alternate MD solvers (use_ours / use_4p4d)"
+        o = options._to_c()
+        c = est_config._to_c()
+        P = len(pairs)
+        if P:
+            offs, X0, X1, D0, D1, MD, C0, C1 = _concat_pairs(variant, pairs)
+        else:
+            offs, X0, X1, D0, D1, MD, C0, C1 = [0], None, None, None, None, None, None, None
+        self._sizes = [offs[p + 1] - offs[p] for p in range(P)]
+        offsets = np.asarray(offs, dtype=np.int64)
+        h = ctypes.c_void_p()
+        dp = lambda a: None if a is None else _dp(a)
+        L.check(L.lib().mp_pair_set_create(variant, P, offsets.ctypes.data_as(L.c_int64_p), dp(X0), dp(X1), dp(D0),
+                                           dp(D1), dp(MD), dp(C0), dp(C1), ctypes.byref(o), ctypes.byref(c),
+                                           self.device, ctypes.byref(h)))
+        self._h = h
+        norm = np.ones(max(P, 1))
+        L.check(L.lib().mp_pair_set_norm_scales(self._h, _dp(norm)))
+        self._norm = norm[:P]
+
+    # ---- lifetime ----
+    def close(self):
+        """Release the set's device memory; idempotent."""
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            L.check(L.lib().mp_pair_set_destroy(h))
+
+    def __enter__(self):
+        self._live()
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (interpreter teardown: the library releases live sets itself)
+            pass
+
+    def _live(self):
+        if getattr(self, "_h", None) is None:
+            raise ValueError("the PairSet is closed")
+        return self._h
+
+    def __len__(self):
+        self._live()
+        return len(self._sizes)
+
+    @property
+    def norm_scale(self):
+        """The pairs' normalization scales (float64, one per pair; 1 for calibrated)."""
+        self._live()
+        return self._norm.copy()
+
+    def _info(self):
+        h = self._live()
+        nc, nb = ctypes.c_int64(), ctypes.c_int64()
+        L.check(L.lib().mp_pair_set_info(h, None, None, ctypes.byref(nc), ctypes.byref(nb), None))
+        return int(nc.value), int(nb.value)
+
+    @property
+    def num_correspondences(self):
+        return self._info()[0]
+
+    @property
+    def resident_bytes(self):
+        """Device bytes of the rows (96 per correspondence) and of the list buffers allocated
+        so far (12 per correspondence each: one after select, two after refine)."""
+        return self._info()[1]
+
+    # ---- the selection ----
+    def _selection(self, pair_ids, count, what):
+        """(ids int32 array or None, its ctypes pointer or None, the selected pairs' sizes, their
+        offsets), checked: `count` entries of `what` must match the selection."""
+        P = len(self._sizes)
+        if pair_ids is None:
+            ids, sizes = None, self._sizes
+        else:
+            ids = np.ascontiguousarray(np.asarray(pair_ids, dtype=np.int64).reshape(-1))
+            seen = set()
+            for j, k in enumerate(ids.tolist()):
+                if not 0 <= k < P:
+                    raise ValueError(f"pair_ids[{j}] = {k} is outside the set of {P} pairs")
+                if k in seen:
+                    raise ValueError(f"pair_ids[{j}] = {k} occurs twice")
+                seen.add(k)
+            ids = ids.astype(np.int32)
+            sizes = [self._sizes[k] for k in ids.tolist()]
+        if count != len(sizes):
+            raise ValueError(f"one {what} per selected pair: {count} for {len(sizes)} pairs")
+        # (an empty selection is answered here, without the library: NULL would mean all pairs)
+        ptr = None if ids is None else ids.ctypes.data_as(L.c_int32_p)
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + n)
+        return ids, ptr, sizes, offs
+
+    # ---- the stages ----
+    def hypothesize(self, samples, pair_ids=None, sample_chunk=0):
+        """hypothesize_batch on the selected pairs: (results, norm_scale) as it returns them."""
+        h = self._live()
+        if self._hyp_error:
+            raise ValueError(self._hyp_error)
+        if isinstance(sample_chunk, bool) or int(sample_chunk) != sample_chunk or sample_chunk < 0:
+            raise ValueError("sample_chunk must be a non-negative integer (0: the default)")
+        ids, ptr, sizes, _ = self._selection(pair_ids, len(samples), "(types, idx)")
+        ns = len(sizes)
+        norm = self._norm.copy() if ids is None else self._norm[ids].copy()
+        if ns == 0:
+            return [], norm
+        slots = L.HYPOTHESIZE_SLOTS[self.variant]
+        soffs, T, I = _concat_samples(self.variant, sizes, samples)
+        S = soffs[-1]
+        sample_offsets = np.asarray(soffs, dtype=np.int64)
+        models = np.zeros((max(S, 1), slots, 17))
+        counts = np.zeros(max(S, 1), dtype=np.int32)
+        L.check(L.lib().mp_hypothesize_set(h, ns, ptr, sample_offsets.ctypes.data_as(L.c_int64_p),
+                                           T.ctypes.data_as(L.c_int32_p), I.ctypes.data_as(L.c_int32_p),
+                                           models.ctypes.data_as(ctypes.POINTER(L.mp_model)),
+                                           counts.ctypes.data_as(L.c_int32_p), int(sample_chunk)))
+        out = [(models[soffs[p]:soffs[p + 1]].copy(), counts[soffs[p]:soffs[p + 1]].copy()) for p in range(ns)]
+        return out, norm
+
+    def select(self, candidates, with_scores=False, with_counts=False, pair_ids=None, model_chunk=0):
+        """select_batch on the selected pairs: one SelectResult per selected pair."""
+        h = self._live()
+        if isinstance(model_chunk, bool) or int(model_chunk) != model_chunk or model_chunk < 0:
+            raise ValueError("model_chunk must be a non-negative integer (0: the default)")
+        ids, ptr, sizes, offs = self._selection(pair_ids, len(candidates), "candidate list")
+        ns = len(sizes)
+        if ns == 0:
+            return []
+        moffs, arr, _keep = _concat_candidates(self.variant, candidates)
+        model_offsets = np.asarray(moffs, dtype=np.int64)
+        M = moffs[-1]
+        res = (L.mp_select_result * ns)()
+        idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
+        scores = np.zeros(max(M, 1), dtype=np.float64) if with_scores else None
+        counts = np.zeros(3 * max(M, 1), dtype=np.int32) if with_counts else None
+        L.check(L.lib().mp_select_set(h, ns, ptr, model_offsets.ctypes.data_as(L.c_int64_p), arr,
+                                      None if scores is None else _dp(scores),
+                                      None if counts is None else counts.ctypes.data_as(L.c_int32_p), res,
+                                      idx.ctypes.data_as(L.c_int32_p), int(model_chunk)))
+        return _select_results(self.variant, candidates, res, idx, offs, moffs, scores, counts)
+
+    def refine(self, models, rounds=1, pair_ids=None):
+        """refine_batch on the selected pairs: one RefineResult per selected pair."""
+        h = self._live()
+        if int(rounds) != rounds or not 1 <= rounds <= 64:
+            raise ValueError("rounds must be an integer in 1..64")
+        ids, ptr, sizes, offs = self._selection(pair_ids, len(models), "model")
+        ns = len(sizes)
+        if ns == 0:
+            return []
+        arr = (L.mp_model * ns)(*[_model_to_c(m, self.variant) for m in models])
+        res = (L.mp_refine_result * ns)()
+        idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
+        L.check(L.lib().mp_refine_set(h, ns, ptr, int(rounds), arr, res, idx.ctypes.data_as(L.c_int32_p)))
+        return _refine_results(self.variant, arr, res, idx, offs)
 
 
 def score_models(variant, x0, x1, depth0, depth1, cam0, cam1, options, est_config, models, with_errors=False,

@@ -10,6 +10,7 @@
 #include "../../include/madpose_mi355x.h"
 #include "host/engine.h"
 #include "host/hypothesis_plan.h"
+#include "host/pair_set_plan.h"
 #include "host/rng.h"
 #include "host/select_plan.h"
 
@@ -274,6 +275,90 @@ int mp_debug_hypothesize_timing(double *out_ms) {
         out_ms[2] = t.upload_ms;
         out_ms[3] = t.solve_ms;
         out_ms[4] = t.download_ms;
+        return MP_OK;
+    });
+}
+
+int mp_pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                       const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                       const double *cam1, const mp_ransac_options *options, const mp_estimator_config *config,
+                       int device, mp_pair_set **out) {
+    return guarded([&]() {
+        static_assert(mp::kPairSetMaxCorr == MP_PAIR_SET_MAX_CORRESPONDENCES, "pair set constants");
+        if (!out) throw std::invalid_argument("null output");
+        *out = nullptr;
+        if (!options) throw std::invalid_argument("null options");
+        *out = reinterpret_cast<mp_pair_set *>(mp::pair_set_create(variant, num_pairs, offsets, x0, x1, d0, d1,
+                                                                   min_depth, cam0, cam1, to_opts(options),
+                                                                   to_cfg(config), device));
+        return MP_OK;
+    });
+}
+
+int mp_pair_set_destroy(mp_pair_set *set) {
+    return guarded([&]() {
+        mp::pair_set_destroy(reinterpret_cast<mp::PairSet *>(set));
+        return MP_OK;
+    });
+}
+
+int mp_pair_set_info(const mp_pair_set *set, int32_t *variant, int32_t *num_pairs, int64_t *correspondences,
+                     int64_t *resident_bytes, int32_t *device) {
+    return guarded([&]() {
+        mp::pair_set_info(reinterpret_cast<const mp::PairSet *>(set), variant, num_pairs, correspondences,
+                          resident_bytes, device);
+        return MP_OK;
+    });
+}
+
+int mp_pair_set_norm_scales(const mp_pair_set *set, double *out) {
+    return guarded([&]() {
+        mp::pair_set_norm_scales(reinterpret_cast<const mp::PairSet *>(set), out);
+        return MP_OK;
+    });
+}
+
+int mp_refine_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int rounds, mp_model *models,
+                  mp_refine_result *results, int32_t *inlier_idx) {
+    return guarded([&]() {
+        mp::refine_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, rounds,
+                       reinterpret_cast<mp::Model *>(models), reinterpret_cast<mp::RefineResult *>(results),
+                       inlier_idx);
+        return MP_OK;
+    });
+}
+
+int mp_select_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
+                  const mp_model *models, double *scores, int32_t *counts, mp_select_result *results,
+                  int32_t *inlier_idx, int64_t model_chunk) {
+    return guarded([&]() {
+        mp::select_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, model_offsets,
+                       reinterpret_cast<const mp::Model *>(models), scores, counts,
+                       reinterpret_cast<mp::SelectResult *>(results), inlier_idx, model_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_hypothesize_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                       const int32_t *sample_types, const int32_t *sample_idx, mp_model *models, int32_t *counts,
+                       int64_t sample_chunk) {
+    return guarded([&]() {
+        mp::hypothesize_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, sample_offsets, sample_types,
+                            sample_idx, reinterpret_cast<mp::Model *>(models), counts, sample_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_debug_pair_set_prep(int mode) {
+    return guarded([&]() {
+        mp::pair_set_prep_mode(mode);
+        return MP_OK;
+    });
+}
+
+int mp_debug_pair_set_rows(const mp_pair_set *set, int32_t pair, double *out) {
+    return guarded([&]() {
+        mp::pair_set_rows(reinterpret_cast<const mp::PairSet *>(set), pair, out);
         return MP_OK;
     });
 }

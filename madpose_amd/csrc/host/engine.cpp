@@ -48,6 +48,7 @@
 #include "env.h"
 #include "hypothesis_plan.h"
 #include "lo_sweep.h"
+#include "pair_set_plan.h"
 #include "refine_plan.h"
 #include "select_plan.h"
 #include "rng.h"
@@ -567,6 +568,17 @@ struct PoolReaper {
         }
     }
 } g_pool_reaper;
+
+// The live pair sets (mp_pair_set_create .. destroy).  At process teardown the sets still
+// open are released while the HIP runtime is alive and before the pooled contexts go
+// (g_set_reaper is defined after g_pool_reaper, so it is destroyed first): a process that
+// exits with a set open exits cleanly.
+std::mutex g_sets_mu;
+std::vector<PairSet *> g_sets;
+void release_live_sets();
+struct SetReaper {
+    ~SetReaper() { release_live_sets(); }
+} g_set_reaper;
 
 // MADPOSE_SEGV_MAPS (diagnostic, presence): on SIGSEGV / SIGBUS write the fault address
 // and /proc/self/maps to stderr, then hand the signal to the handler installed before
@@ -2480,14 +2492,208 @@ void lm_refine_batch_device(const PairInput &in, const RansacOptions &opts, cons
     }
 }
 
+#include "resident_pairs.h"
+
+namespace {
+// Refinement of the models of the selected resident pairs (refine_batch's rounds; the body of
+// mp_refine_batch and mp_refine_set).  models / results: entry j of the selection; the
+// accepted models' lists of entry j to inlier_idx + 3 out_off[j] + t n_j (nullable).
+// Per-call state only: each pair's list buffer choice starts at 0, and the lists read are
+// the ones this call wrote.
+void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const int64_t *out_off,
+                const EstimatorConfig &cfg, int rounds, Model *models, RefineResult *results, int32_t *inlier_idx) {
+    const int ns = sel.n;
+    if (ns == 0) return;
+    const int variant = R.variant, v = R.v;
+    const int kmd = v == kCal ? 3 : 4, kpt = v == kCal ? 5 : (v == kSF ? 6 : 7);
+    const int64_t T = R.T;
+    int *d_lists = R.lists(2);
+    const std::vector<PairConst> &Ch = R.Ch;
+
+    // ---- per-pair state (models in problem units) ----
+    std::vector<Model> cur(ns);
+    std::vector<double> score(ns, 0.0);
+    std::vector<int> buf(ns, 0);
+    for (int j = 0; j < ns; ++j) {
+        const int k = sel[j];
+        cur[j] = models[j];
+        if (variant == kSF || variant == kTF) {
+            cur[j].focal0 /= R.norm_scale[k];
+            cur[j].focal1 /= R.norm_scale[k];
+        }
+        RefineResult &Q = results[j];
+        std::memset(&Q, 0, sizeof(Q));
+        Q.norm_scale = R.norm_scale[k];
+        Q.lm_status = -1;
+    }
+    DevArray<RefineItem> d_items(ns);
+    DevArray<ScoreRec> d_recs(ns);
+    DevArray<RefineSweepOut> d_out(ns);
+    DevArray<LmJob> d_jobs(ns);
+    DevArray<LmPairRef> d_refs(ns);
+    DevArray<Model> d_models(ns);
+    DevArray<int> d_status(ns);
+    std::vector<RefineItem> items;
+    std::vector<ScoreRec> recs;
+    std::vector<RefineSweepOut> outs;
+    // one sweep launch: model ms[i] of selection entry js[i], lists into the buffer items[i].buf
+    auto sweep = [&](const std::vector<int> &js, const std::vector<Model> &ms, bool other_buf) {
+        const size_t m = js.size();
+        items.resize(m);
+        recs.resize(m);
+        outs.resize(m);
+        if (m == 0) return;
+        for (size_t i = 0; i < m; ++i) {
+            items[i].pair = sel[js[i]];
+            items[i].buf = other_buf ? buf[js[i]] ^ 1 : buf[js[i]];
+            prepare_score_rec(Ch[sel[js[i]]], ms[i], recs[i]);
+        }
+        MP_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(RefineItem) * m, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_recs.p, recs.data(), sizeof(ScoreRec) * m, hipMemcpyHostToDevice, stream));
+        MP_HIP(launch_refine_sweep(stream, v, R.d_D.p, R.d_C.p, d_items.p, d_recs.p, (int)m, R.d_list_off.p, d_lists,
+                                   3 * T, d_out.p));
+        MP_HIP(hipMemcpyAsync(outs.data(), d_out.p, sizeof(RefineSweepOut) * m, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+    };
+
+    // ---- the initial sweep: score and lists of the given models ----
+    std::vector<int> running(ns);
+    for (int j = 0; j < ns; ++j) running[j] = j;
+    sweep(running, cur, false);
+    for (int j = 0; j < ns; ++j) {
+        RefineResult &Q = results[j];
+        score[j] = Q.score_initial = Q.score_final = outs[j].score;
+        for (int t = 0; t < 3; ++t) Q.num_inliers[t] = outs[j].count[t];
+    }
+    // ---- rounds ----
+    std::vector<LmJob> jobs;
+    std::vector<LmPairRef> refs;
+    std::vector<int> which, st, cand_j;
+    std::vector<Model> lm_out, cand_m;
+    for (int round = 0; round < rounds && !running.empty(); ++round) {
+        jobs.clear();
+        refs.clear();
+        which.clear();
+        for (int j : running) {
+            const int k = sel[j];
+            RefineResult &Q = results[j];
+            ++Q.rounds_run;
+            const int *sz = Q.num_inliers;
+            // too few data for the solver (the size test of least_squares): the pair stops
+            if ((sz[0] < kmd && sz[1] < kmd) || sz[2] < kpt) {
+                Q.lm_status = 3;
+                continue;
+            }
+            LmJob J = make_lm_job(R.Ps[k], cfg, sz, 0, false, cur[j]);
+            // (the lists of a pair lie n apart, not back to back)
+            J.off1 = Ch[k].n;
+            J.off2 = 2 * Ch[k].n;
+            jobs.push_back(J);
+            LmPairRef ref;
+            ref.pair = k;
+            ref.pad = 0;
+            ref.idx_off = refine_list(T, R.off[k], Ch[k].n, buf[j], 0);
+            refs.push_back(ref);
+            which.push_back(j);
+        }
+        running.clear();
+        if (jobs.empty()) break;
+        const size_t nj = jobs.size();
+        lm_out.resize(nj);
+        st.resize(nj);
+        MP_HIP(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(LmJob) * nj, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_refs.p, refs.data(), sizeof(LmPairRef) * nj, hipMemcpyHostToDevice, stream));
+        MP_HIP(launch_lm_pairs(stream, v, R.d_D.p, R.d_C.p, d_jobs.p, d_refs.p, (int)nj, d_lists, d_models.p,
+                               d_status.p));
+        MP_HIP(hipMemcpyAsync(lm_out.data(), d_models.p, sizeof(Model) * nj, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipMemcpyAsync(st.data(), d_status.p, sizeof(int) * nj, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+        cand_j.clear();
+        cand_m.clear();
+        for (size_t i = 0; i < nj; ++i) {
+            results[which[i]].lm_status = st[i];
+            if (st[i] != 1) continue; // (model unchanged: the pair stops)
+            cand_j.push_back(which[i]);
+            cand_m.push_back(lm_out[i]);
+        }
+        // the candidates' scores and lists, into each pair's other list buffer
+        sweep(cand_j, cand_m, true);
+        for (size_t i = 0; i < cand_j.size(); ++i) {
+            const int j = cand_j[i];
+            if (!(outs[i].score < score[j])) continue; // (not strictly lower: the pair stops)
+            RefineResult &Q = results[j];
+            cur[j] = cand_m[i];
+            score[j] = Q.score_final = outs[i].score;
+            for (int t = 0; t < 3; ++t) Q.num_inliers[t] = outs[i].count[t];
+            buf[j] ^= 1;
+            ++Q.rounds_accepted;
+            running.push_back(j);
+        }
+    }
+    // ---- results: models back in user units, the accepted models' lists ----
+    for (int j = 0; j < ns; ++j) {
+        if (results[j].rounds_accepted == 0) continue; // (the given model, untouched)
+        const double norm = R.norm_scale[sel[j]];
+        Model m = cur[j];
+        if (variant == kSF) {
+            m.focal0 *= norm;
+            m.focal1 = m.focal0;
+        } else if (variant == kTF) {
+            m.focal0 *= norm;
+            m.focal1 *= norm;
+        }
+        models[j] = m;
+    }
+    if (inlier_idx && T > 0) {
+        if (!sel.ids) { // every pair: the buffers in one copy
+            const bool both = std::any_of(buf.begin(), buf.end(), [](int b) { return b != 0; });
+            std::vector<int> lists((both ? 6 : 3) * (size_t)T);
+            MP_HIP(hipMemcpyAsync(lists.data(), d_lists, sizeof(int) * lists.size(), hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipStreamSynchronize(stream));
+            for (int j = 0; j < ns; ++j) {
+                const int64_t n = Ch[j].n;
+                for (int t = 0; t < 3; ++t)
+                    std::memcpy(inlier_idx + 3 * out_off[j] + t * n, lists.data() + refine_list(T, R.off[j], n, buf[j], t),
+                                sizeof(int) * (size_t)results[j].num_inliers[t]);
+            }
+        } else { // a selection: only its pairs' lists
+            for (int j = 0; j < ns; ++j) {
+                const int k = sel[j];
+                const int64_t n = Ch[k].n;
+                for (int t = 0; t < 3; ++t)
+                    if (results[j].num_inliers[t] > 0)
+                        MP_HIP(hipMemcpyAsync(inlier_idx + 3 * out_off[j] + t * n,
+                                              d_lists + refine_list(T, R.off[k], n, buf[j], t),
+                                              sizeof(int) * (size_t)results[j].num_inliers[t], hipMemcpyDeviceToHost,
+                                              stream));
+            }
+        }
+    }
+    MP_HIP(hipStreamSynchronize(stream));
+}
+
+// the argument checks refine_batch and the pair set's creation share (all before any array
+// is read beyond offsets, and before the device is touched)
+void check_pair_arrays(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                       const double *d0, const double *d1) {
+    if (offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+    for (int32_t p = 0; p < num_pairs; ++p) {
+        if (offsets[p + 1] < offsets[p]) throw std::invalid_argument("offsets must not decrease");
+        if (offsets[p + 1] - offsets[p] > kRefinePairMax) throw std::invalid_argument("pair too large");
+    }
+    if (offsets[num_pairs] > 0 && (!x0 || !x1 || !d0 || !d1)) throw std::invalid_argument("null input array");
+}
+} // namespace
+
 // Refinement of given models over many pairs (mp_refine_batch).  Per pair and round: the
 // inliers of the model (errors of launch_sweep below the thresholds), LeastSquares over
 // all of them on the device LM, and the result kept when it scores strictly lower
 // (LeastSquaresFit with use_all_solver_inliers and the final least squares' score <
 // best rule, src/hybrid_ransac.h:406, 484-510, 186-203).  The pairs of a run
-// (host/refine_plan.h) are resident at once; a round is one LM launch and one sweep
-// launch over the pairs still running, and the sweep that decides round r is the inlier
-// pass of round r + 1.  The host only drops stopped pairs from the launch lists.
+// (host/refine_plan.h) are resident at once (host/resident_pairs.h); a round is one LM
+// launch and one sweep launch over the pairs still running, and the sweep that decides
+// round r is the inlier pass of round r + 1.  The host only drops stopped pairs from the
+// launch lists.
 void refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
                   const double *d0, const double *d1, const double *min_depth, const double *cam0, const double *cam1,
                   const RansacOptions &opts, const EstimatorConfig &cfg, int rounds, Model *models,
@@ -2504,236 +2710,17 @@ void refine_batch(int variant, int32_t num_pairs, const int64_t *offsets, const 
     if (num_pairs == 0) return;
     if (!offsets || !min_depth || !cam0 || !cam1 || !models || !results)
         throw std::invalid_argument("null offsets, min_depth, cameras, models or results");
-    if (offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
-    for (int32_t p = 0; p < num_pairs; ++p) {
-        if (offsets[p + 1] < offsets[p]) throw std::invalid_argument("offsets must not decrease");
-        if (offsets[p + 1] - offsets[p] > kRefinePairMax) throw std::invalid_argument("pair too large");
-    }
-    if (offsets[num_pairs] > 0 && (!x0 || !x1 || !d0 || !d1)) throw std::invalid_argument("null input array");
+    check_pair_arrays(variant, num_pairs, offsets, x0, x1, d0, d1);
 
     const int nc = (variant == kCal || variant == kScaleOnly) ? 9 : 2;
-    const int v = variant == kScaleOnly ? kCal : variant;
-    const int kmd = v == kCal ? 3 : 4, kpt = v == kCal ? 5 : (v == kSF ? 6 : 7);
     CtxLease lease(device);
     hipStream_t stream = lease.c->stream;
-
     for (const RefineRun &run : refine_plan(num_pairs, offsets, chunk)) {
         const int np = run.p1 - run.p0;
-        const int64_t T = run.total;
-        // ---- problems, packed upload, pair records ----
-        std::vector<Problem> Ps(np);
-        std::vector<PairData> Dh(np);
-        std::vector<PairConst> Ch(np);
-        std::vector<int64_t> off(np), list_off(np);
-        std::vector<double> stage(6 * (size_t)T);
-        DevArray<double> d_data((size_t)kRefineRows * T);
-        DevArray<int> d_lists(6 * (size_t)T);
-        for (int k = 0; k < np; ++k) {
-            const int32_t p = run.p0 + k;
-            const int64_t o = offsets[p], n = offsets[p + 1] - o;
-            PairInput in;
-            in.variant = variant;
-            in.n = n;
-            in.x0 = x0 + 2 * o;
-            in.x1 = x1 + 2 * o;
-            in.d0 = d0 + o;
-            in.d1 = d1 + o;
-            in.min_depth[0] = min_depth[2 * p];
-            in.min_depth[1] = min_depth[2 * p + 1];
-            std::memcpy(in.cam0, cam0 + (size_t)nc * p, sizeof(double) * nc);
-            std::memcpy(in.cam1, cam1 + (size_t)nc * p, sizeof(double) * nc);
-            Problem &P = Ps[k];
-            P = make_problem(in, opts, cfg);
-            off[k] = o - offsets[run.p0];
-            list_off[k] = 3 * off[k];
-            refine_pack_pair(P.H.x0.data(), P.H.x1.data(), P.H.d0.data(), P.H.d1.data(), n, off[k], stage.data());
-            // (the host copies are not needed again: the LM runs on the device)
-            P.H.x0 = std::vector<double>();
-            P.H.x1 = std::vector<double>();
-            P.H.d0 = std::vector<double>();
-            P.H.d1 = std::vector<double>();
-            const double *rows[kRefineRows];
-            for (int r = 0; r < kRefineRows; ++r) rows[r] = d_data.p + refine_row(T, off[k], n, r);
-            PairData &D = Dh[k];
-            D.x0u = rows[0];
-            D.x0v = rows[1];
-            D.x1u = rows[2];
-            D.x1v = rows[3];
-            D.d0 = rows[4];
-            D.d1 = rows[5];
-            D.r0 = rows[6];
-            D.r1 = rows[7];
-            D.a0 = rows[8];
-            D.a1 = rows[9];
-            D.b0 = rows[10];
-            D.b1 = rows[11];
-            Ch[k] = P.C;
-        }
-        DevArray<PairData> d_D(np);
-        DevArray<PairConst> d_C(np);
-        DevArray<int64_t> d_list_off(np);
-        if (T > 0)
-            MP_HIP(hipMemcpyAsync(d_data.p, stage.data(), sizeof(double) * 6 * (size_t)T, hipMemcpyHostToDevice,
-                                  stream));
-        MP_HIP(hipMemcpyAsync(d_D.p, Dh.data(), sizeof(PairData) * np, hipMemcpyHostToDevice, stream));
-        MP_HIP(hipMemcpyAsync(d_C.p, Ch.data(), sizeof(PairConst) * np, hipMemcpyHostToDevice, stream));
-        MP_HIP(hipMemcpyAsync(d_list_off.p, list_off.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice, stream));
-        // pair preparation (the calibrated bearings and rays; the other variants read none)
-        if (v == kCal)
-            for (int k = 0; k < np; ++k) {
-                double *base = d_data.p;
-                const int64_t n = Ch[k].n;
-                auto row = [&](int r) { return base + refine_row(T, off[k], n, r); };
-                MP_HIP(launch_prep_pair(stream, Ch[k], Dh[k], row(6), row(7), row(8), row(9), row(10), row(11)));
-            }
-
-        // ---- per-pair state (models in problem units) ----
-        std::vector<Model> cur(np);
-        std::vector<double> score(np, 0.0);
-        std::vector<int> buf(np, 0);
-        for (int k = 0; k < np; ++k) {
-            const int32_t p = run.p0 + k;
-            cur[k] = models[p];
-            if (variant == kSF || variant == kTF) {
-                cur[k].focal0 /= Ps[k].norm_scale;
-                cur[k].focal1 /= Ps[k].norm_scale;
-            }
-            RefineResult &R = results[p];
-            std::memset(&R, 0, sizeof(R));
-            R.norm_scale = Ps[k].norm_scale;
-            R.lm_status = -1;
-        }
-        DevArray<RefineItem> d_items(np);
-        DevArray<ScoreRec> d_recs(np);
-        DevArray<RefineSweepOut> d_out(np);
-        DevArray<LmJob> d_jobs(np);
-        DevArray<LmPairRef> d_refs(np);
-        DevArray<Model> d_models(np);
-        DevArray<int> d_status(np);
-        std::vector<RefineItem> items;
-        std::vector<ScoreRec> recs;
-        std::vector<RefineSweepOut> outs;
-        // one sweep launch: model ms[j] of pair ks[j], lists into the buffer items[j].buf
-        auto sweep = [&](const std::vector<int> &ks, const std::vector<Model> &ms, bool other_buf) {
-            const size_t m = ks.size();
-            items.resize(m);
-            recs.resize(m);
-            outs.resize(m);
-            if (m == 0) return;
-            for (size_t j = 0; j < m; ++j) {
-                items[j].pair = ks[j];
-                items[j].buf = other_buf ? buf[ks[j]] ^ 1 : buf[ks[j]];
-                prepare_score_rec(Ch[ks[j]], ms[j], recs[j]);
-            }
-            MP_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(RefineItem) * m, hipMemcpyHostToDevice, stream));
-            MP_HIP(hipMemcpyAsync(d_recs.p, recs.data(), sizeof(ScoreRec) * m, hipMemcpyHostToDevice, stream));
-            MP_HIP(launch_refine_sweep(stream, v, d_D.p, d_C.p, d_items.p, d_recs.p, (int)m, d_list_off.p, d_lists.p,
-                                       3 * T, d_out.p));
-            MP_HIP(hipMemcpyAsync(outs.data(), d_out.p, sizeof(RefineSweepOut) * m, hipMemcpyDeviceToHost, stream));
-            MP_HIP(hipStreamSynchronize(stream));
-        };
-
-        // ---- the initial sweep: score and lists of the given models ----
-        std::vector<int> running(np);
-        for (int k = 0; k < np; ++k) running[k] = k;
-        sweep(running, cur, false);
-        for (int k = 0; k < np; ++k) {
-            RefineResult &R = results[run.p0 + k];
-            score[k] = R.score_initial = R.score_final = outs[k].score;
-            for (int t = 0; t < 3; ++t) R.num_inliers[t] = outs[k].count[t];
-        }
-        // ---- rounds ----
-        std::vector<LmJob> jobs;
-        std::vector<LmPairRef> refs;
-        std::vector<int> which, st, cand_k;
-        std::vector<Model> lm_out, cand_m;
-        for (int round = 0; round < rounds && !running.empty(); ++round) {
-            jobs.clear();
-            refs.clear();
-            which.clear();
-            for (int k : running) {
-                RefineResult &R = results[run.p0 + k];
-                ++R.rounds_run;
-                const int *sz = R.num_inliers;
-                // too few data for the solver (the size test of least_squares): the pair stops
-                if ((sz[0] < kmd && sz[1] < kmd) || sz[2] < kpt) {
-                    R.lm_status = 3;
-                    continue;
-                }
-                LmJob J = make_lm_job(Ps[k], cfg, sz, 0, false, cur[k]);
-                // (the lists of a pair lie n apart, not back to back)
-                J.off1 = Ch[k].n;
-                J.off2 = 2 * Ch[k].n;
-                jobs.push_back(J);
-                LmPairRef ref;
-                ref.pair = k;
-                ref.pad = 0;
-                ref.idx_off = refine_list(T, off[k], Ch[k].n, buf[k], 0);
-                refs.push_back(ref);
-                which.push_back(k);
-            }
-            running.clear();
-            if (jobs.empty()) break;
-            const size_t nj = jobs.size();
-            lm_out.resize(nj);
-            st.resize(nj);
-            MP_HIP(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(LmJob) * nj, hipMemcpyHostToDevice, stream));
-            MP_HIP(hipMemcpyAsync(d_refs.p, refs.data(), sizeof(LmPairRef) * nj, hipMemcpyHostToDevice, stream));
-            MP_HIP(launch_lm_pairs(stream, v, d_D.p, d_C.p, d_jobs.p, d_refs.p, (int)nj, d_lists.p, d_models.p,
-                                   d_status.p));
-            MP_HIP(hipMemcpyAsync(lm_out.data(), d_models.p, sizeof(Model) * nj, hipMemcpyDeviceToHost, stream));
-            MP_HIP(hipMemcpyAsync(st.data(), d_status.p, sizeof(int) * nj, hipMemcpyDeviceToHost, stream));
-            MP_HIP(hipStreamSynchronize(stream));
-            cand_k.clear();
-            cand_m.clear();
-            for (size_t j = 0; j < nj; ++j) {
-                results[run.p0 + which[j]].lm_status = st[j];
-                if (st[j] != 1) continue; // (model unchanged: the pair stops)
-                cand_k.push_back(which[j]);
-                cand_m.push_back(lm_out[j]);
-            }
-            // the candidates' scores and lists, into each pair's other list buffer
-            sweep(cand_k, cand_m, true);
-            for (size_t j = 0; j < cand_k.size(); ++j) {
-                const int k = cand_k[j];
-                if (!(outs[j].score < score[k])) continue; // (not strictly lower: the pair stops)
-                RefineResult &R = results[run.p0 + k];
-                cur[k] = cand_m[j];
-                score[k] = R.score_final = outs[j].score;
-                for (int t = 0; t < 3; ++t) R.num_inliers[t] = outs[j].count[t];
-                buf[k] ^= 1;
-                ++R.rounds_accepted;
-                running.push_back(k);
-            }
-        }
-        // ---- results: models back in user units, the accepted models' lists ----
-        for (int k = 0; k < np; ++k) {
-            const int32_t p = run.p0 + k;
-            if (results[p].rounds_accepted == 0) continue; // (the given model, untouched)
-            Model m = cur[k];
-            if (variant == kSF) {
-                m.focal0 *= Ps[k].norm_scale;
-                m.focal1 = m.focal0;
-            } else if (variant == kTF) {
-                m.focal0 *= Ps[k].norm_scale;
-                m.focal1 *= Ps[k].norm_scale;
-            }
-            models[p] = m;
-        }
-        if (inlier_idx && T > 0) {
-            const bool both = std::any_of(buf.begin(), buf.end(), [](int b) { return b != 0; });
-            std::vector<int> lists((both ? 6 : 3) * (size_t)T);
-            MP_HIP(hipMemcpyAsync(lists.data(), d_lists.p, sizeof(int) * lists.size(), hipMemcpyDeviceToHost, stream));
-            MP_HIP(hipStreamSynchronize(stream));
-            for (int k = 0; k < np; ++k) {
-                const int32_t p = run.p0 + k;
-                const int64_t n = Ch[k].n;
-                for (int t = 0; t < 3; ++t)
-                    std::memcpy(inlier_idx + 3 * offsets[p] + t * n, lists.data() + refine_list(T, off[k], n, buf[k], t),
-                                sizeof(int) * (size_t)results[p].num_inliers[t]);
-            }
-        }
-        MP_HIP(hipStreamSynchronize(stream));
+        ResidentPairs R(stream, variant, np, offsets + run.p0, x0, x1, d0, d1, min_depth + 2 * (size_t)run.p0,
+                        cam0 + (size_t)nc * run.p0, cam1 + (size_t)nc * run.p0, opts, cfg);
+        refine_run(R, stream, PairSel{np, nullptr}, offsets + run.p0, cfg, rounds, models + run.p0,
+                   results + run.p0, inlier_idx);
     }
 }
 
@@ -2774,6 +2761,200 @@ SelectTiming select_timing_last() {
     return g_select_timing;
 }
 
+namespace {
+// Ranking of the candidates of the selected resident pairs (the body of mp_select_batch and
+// mp_select_set).  moff: ns + 1 offsets into models / scores / counts (entry j's candidates
+// at moff[j] .. moff[j + 1] - 1); results: entry j; the winner's lists of entry j to
+// inlier_idx + 3 out_off[j] + t n_j (nullable).  List buffer 0 is scratch of the call.
+void select_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const int64_t *out_off, const int64_t *moff,
+                const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
+                int64_t model_chunk, int tile, bool timed, SelectTiming &tm) {
+    const int ns = sel.n;
+    if (ns == 0) return;
+    const int variant = R.variant, v = R.v;
+    const int64_t T = R.T;
+    const int64_t M = moff[ns] - moff[0];
+    const std::vector<PairConst> &Ch = R.Ch;
+    // (timed: every stage is waited for, so the parts add up and nothing overlaps)
+    auto stage_end = [&](Clock::time_point t0, double &ms) {
+        if (!timed) return;
+        MP_HIP(hipStreamSynchronize(stream));
+        ms += 1e3 * secs(t0);
+    };
+    Clock::time_point t0 = Clock::now();
+    int *d_lists = R.lists(1);
+    std::vector<int64_t> moff_run(ns + 1);
+    for (int j = 0; j <= ns; ++j) moff_run[j] = moff[j] - moff[0];
+    DevArray<int64_t> d_moff(ns + 1);
+    MP_HIP(hipMemcpyAsync(d_moff.p, moff_run.data(), sizeof(int64_t) * (ns + 1), hipMemcpyHostToDevice, stream));
+    stage_end(t0, tm.pairs_ms);
+
+    // the model of candidate m of the call in problem units (entry j of the selection)
+    auto problem_model = [&](int j, int64_t m) {
+        Model c = models[moff[0] + m];
+        if (variant == kSF || variant == kTF) {
+            const double norm = R.norm_scale[sel[j]];
+            c.focal0 /= norm;
+            c.focal1 /= norm;
+        }
+        return c;
+    };
+    // ---- the candidates' scores and counts, slab by slab ----
+    DevArray<double> d_scores((size_t)M);
+    DevArray<int> d_counts(3 * (size_t)M);
+    const std::vector<SelectSlab> slabs = select_slabs(M, model_chunk);
+    const size_t cap = slabs.empty() ? 0 : (size_t)(slabs[0].m1 - slabs[0].m0); // (the first is the largest)
+    const int nbuf = slabs.size() > 1 ? 2 : 1;
+    // (a work item holds at least one candidate: a slab has at most `cap` items)
+    std::unique_ptr<PinnedArray<ScoreRec>> h_recs[2];
+    std::unique_ptr<PinnedArray<SelectItem>> h_items[2];
+    std::unique_ptr<DevArray<ScoreRec>> d_recs[2];
+    std::unique_ptr<DevArray<SelectItem>> d_items[2];
+    std::unique_ptr<EventHolder> uploaded[2], scored[2];
+    for (int b = 0; b < nbuf && cap > 0; ++b) {
+        h_recs[b].reset(new PinnedArray<ScoreRec>(cap));
+        h_items[b].reset(new PinnedArray<SelectItem>(cap));
+        d_recs[b].reset(new DevArray<ScoreRec>(cap));
+        d_items[b].reset(new DevArray<SelectItem>(cap));
+        uploaded[b].reset(new EventHolder());
+        scored[b].reset(new EventHolder());
+    }
+    std::vector<SelectItem> items;
+    for (size_t si = 0; si < slabs.size(); ++si) {
+        const SelectSlab &s = slabs[si];
+        const int b = (int)(si % 2) % nbuf;
+        const int64_t nslab = s.m1 - s.m0;
+        // (the host buffers' previous upload and the device buffers' previous launch are over)
+        if (si >= 2) {
+            MP_HIP(hipEventSynchronize(uploaded[b]->e));
+            MP_HIP(hipEventSynchronize(scored[b]->e));
+        }
+        t0 = Clock::now();
+        select_items(ns, moff, s, tile, items);
+        // (the plan names the selection's entries; the kernels index the resident records)
+        if (sel.ids)
+            for (SelectItem &it : items) it.pair = sel.ids[it.pair];
+        std::memcpy(h_items[b]->p, items.data(), sizeof(SelectItem) * items.size());
+        ScoreRec *recs = h_recs[b]->p;
+        // candidates a .. e - 1 of the slab; the entry of each by a walk from the first one's
+        auto prepare = [&](int64_t a, int64_t e) {
+            int j = (int)(std::upper_bound(moff_run.begin(), moff_run.end(), s.m0 + a) - moff_run.begin()) - 1;
+            for (int64_t q = a; q < e; ++q) {
+                const int64_t m = s.m0 + q;
+                while (moff_run[j + 1] <= m) ++j;
+                const Model c = problem_model(j, m);
+                prepare_score_rec(Ch[sel[j]], c, recs[q]);
+            }
+        };
+        const int nthr = (int)std::min<int64_t>(kSelectPrepThreads, nslab / kSelectPrepPerThread);
+        if (nthr <= 1) {
+            prepare(0, nslab);
+        } else {
+            std::vector<std::thread> threads;
+            for (int t = 1; t < nthr; ++t) threads.emplace_back(prepare, nslab * t / nthr, nslab * (t + 1) / nthr);
+            prepare(0, nslab / nthr);
+            for (auto &t : threads) t.join();
+        }
+        if (timed) tm.prepare_ms += 1e3 * secs(t0);
+        t0 = Clock::now();
+        MP_HIP(hipMemcpyAsync(d_recs[b]->p, recs, sizeof(ScoreRec) * (size_t)nslab, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_items[b]->p, h_items[b]->p, sizeof(SelectItem) * items.size(), hipMemcpyHostToDevice,
+                              stream));
+        MP_HIP(hipEventRecord(uploaded[b]->e, stream));
+        stage_end(t0, tm.upload_ms);
+        t0 = Clock::now();
+        MP_HIP(launch_select_score(stream, v, tile, R.d_D.p, R.d_C.p, d_items[b]->p, (int)items.size(), d_recs[b]->p,
+                                   s.m0, d_scores.p, d_counts.p));
+        MP_HIP(hipEventRecord(scored[b]->e, stream));
+        stage_end(t0, tm.score_ms);
+    }
+    // ---- the best candidate of every pair ----
+    t0 = Clock::now();
+    DevArray<SelectBest> d_best(ns);
+    std::vector<SelectBest> best(ns);
+    MP_HIP(launch_select_argmin(stream, d_moff.p, ns, d_scores.p, d_best.p));
+    MP_HIP(hipMemcpyAsync(best.data(), d_best.p, sizeof(SelectBest) * ns, hipMemcpyDeviceToHost, stream));
+    if (scores && M > 0)
+        MP_HIP(hipMemcpyAsync(scores + moff[0], d_scores.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, stream));
+    if (counts && M > 0)
+        MP_HIP(hipMemcpyAsync(counts + 3 * moff[0], d_counts.p, sizeof(int) * 3 * (size_t)M, hipMemcpyDeviceToHost,
+                              stream));
+    MP_HIP(hipStreamSynchronize(stream));
+    if (timed) tm.argmin_ms += 1e3 * secs(t0);
+    // ---- the winners' lists: refine_batch's sweep, one item per pair with a winner ----
+    t0 = Clock::now();
+    std::vector<RefineItem> ritems;
+    std::vector<ScoreRec> rrecs;
+    std::vector<int> which;
+    for (int j = 0; j < ns; ++j) {
+        SelectResult &Q = results[j];
+        std::memset(&Q, 0, sizeof(Q));
+        Q.best_score = DBL_MAX;
+        Q.norm_scale = R.norm_scale[sel[j]];
+        Q.best_index = -1;
+        if (best[j].index < 0) continue;
+        if (best[j].index >= moff[j + 1] - moff[j]) throw std::runtime_error("select_argmin: index out of range");
+        RefineItem it;
+        it.pair = sel[j];
+        it.buf = 0;
+        ritems.push_back(it);
+        rrecs.emplace_back();
+        prepare_score_rec(Ch[sel[j]], problem_model(j, moff_run[j] + best[j].index), rrecs.back());
+        which.push_back(j);
+    }
+    const size_t nw = which.size();
+    if (nw > 0) {
+        DevArray<RefineItem> d_ritems(nw);
+        DevArray<ScoreRec> d_rrecs(nw);
+        DevArray<RefineSweepOut> d_out(nw);
+        std::vector<RefineSweepOut> outs(nw);
+        MP_HIP(hipMemcpyAsync(d_ritems.p, ritems.data(), sizeof(RefineItem) * nw, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_rrecs.p, rrecs.data(), sizeof(ScoreRec) * nw, hipMemcpyHostToDevice, stream));
+        MP_HIP(launch_refine_sweep(stream, v, R.d_D.p, R.d_C.p, d_ritems.p, d_rrecs.p, (int)nw, R.d_list_off.p, d_lists,
+                                   3 * T, d_out.p));
+        MP_HIP(hipMemcpyAsync(outs.data(), d_out.p, sizeof(RefineSweepOut) * nw, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+        for (size_t i = 0; i < nw; ++i) {
+            const int j = which[i];
+            SelectResult &Q = results[j];
+            // (the same record through the same arithmetic: anything else is a defect; the
+            // measurement hook's other work-item sizes are not pinned to these bits)
+            if (tile == kSelectTile && std::memcmp(&outs[i].score, &best[j].score, sizeof(double)) != 0)
+                throw std::runtime_error("select_batch: the winner's sweep score differs from its selected score");
+            Q.best_score = best[j].score;
+            Q.best_index = best[j].index;
+            for (int t = 0; t < 3; ++t) Q.num_inliers[t] = outs[i].count[t];
+        }
+        if (inlier_idx && T > 0) {
+            if (!sel.ids) { // every pair: the buffer in one copy
+                std::vector<int> lists(3 * (size_t)T);
+                MP_HIP(hipMemcpyAsync(lists.data(), d_lists, sizeof(int) * lists.size(), hipMemcpyDeviceToHost, stream));
+                MP_HIP(hipStreamSynchronize(stream));
+                for (int j : which) {
+                    const int64_t n = Ch[j].n;
+                    for (int t = 0; t < 3; ++t)
+                        std::memcpy(inlier_idx + 3 * out_off[j] + t * n, lists.data() + refine_list(T, R.off[j], n, 0, t),
+                                    sizeof(int) * (size_t)results[j].num_inliers[t]);
+                }
+            } else { // a selection: only its winners' lists
+                for (int j : which) {
+                    const int k = sel[j];
+                    const int64_t n = Ch[k].n;
+                    for (int t = 0; t < 3; ++t)
+                        if (results[j].num_inliers[t] > 0)
+                            MP_HIP(hipMemcpyAsync(inlier_idx + 3 * out_off[j] + t * n,
+                                                  d_lists + refine_list(T, R.off[k], n, 0, t),
+                                                  sizeof(int) * (size_t)results[j].num_inliers[t],
+                                                  hipMemcpyDeviceToHost, stream));
+                }
+            }
+        }
+    }
+    MP_HIP(hipStreamSynchronize(stream));
+    if (timed) tm.winners_ms += 1e3 * secs(t0);
+}
+} // namespace
+
 // Ranking of given candidate models over many pairs (mp_select_batch).  The pairs of a run
 // (host/refine_plan.h) are resident at once.  Per run: the candidates' score records,
 // prepared on the host (prepare_score_rec: mp_score_models' bits), go to the device in
@@ -2809,238 +2990,22 @@ void select_batch(int variant, int32_t num_pairs, const int64_t *offsets, const 
     if (model_offsets[num_pairs] > model_offsets[0] && !models) throw std::invalid_argument("null models");
 
     const int nc = (variant == kCal || variant == kScaleOnly) ? 9 : 2;
-    const int v = variant == kScaleOnly ? kCal : variant;
     const int tile_set = g_select_tile.load();
     const int tile = tile_set ? tile_set : kSelectTile;
     const bool timed = g_prof_on.load();
     SelectTiming tm;
     CtxLease lease(device);
     hipStream_t stream = lease.c->stream;
-    // (timed: every stage is waited for, so the parts add up and nothing overlaps)
-    auto stage_end = [&](Clock::time_point t0, double &ms) {
-        if (!timed) return;
-        MP_HIP(hipStreamSynchronize(stream));
-        ms += 1e3 * secs(t0);
-    };
 
     for (const RefineRun &run : refine_plan(num_pairs, offsets, chunk)) {
         const int np = run.p1 - run.p0;
-        const int64_t T = run.total;
-        const int64_t *moff = model_offsets + run.p0; // np + 1 values; candidate 0 of the run at moff[0]
-        const int64_t M = moff[np] - moff[0];
-        // ---- problems, packed upload, pair records (as refine_batch; one list buffer) ----
+        // ---- problems, packed upload, pair records (host/resident_pairs.h) ----
         Clock::time_point t0 = Clock::now();
-        std::vector<double> norm(np);
-        std::vector<PairData> Dh(np);
-        std::vector<PairConst> Ch(np);
-        std::vector<int64_t> off(np), list_off(np), moff_run(np + 1);
-        std::vector<double> stage(6 * (size_t)T);
-        DevArray<double> d_data((size_t)kRefineRows * T);
-        DevArray<int> d_lists(3 * (size_t)T);
-        for (int k = 0; k < np; ++k) {
-            const int32_t p = run.p0 + k;
-            const int64_t o = offsets[p], n = offsets[p + 1] - o;
-            PairInput in;
-            in.variant = variant;
-            in.n = n;
-            in.x0 = x0 + 2 * o;
-            in.x1 = x1 + 2 * o;
-            in.d0 = d0 + o;
-            in.d1 = d1 + o;
-            std::memcpy(in.cam0, cam0 + (size_t)nc * p, sizeof(double) * nc);
-            std::memcpy(in.cam1, cam1 + (size_t)nc * p, sizeof(double) * nc);
-            const Problem P = make_problem(in, opts, cfg);
-            off[k] = o - offsets[run.p0];
-            list_off[k] = 3 * off[k];
-            refine_pack_pair(P.H.x0.data(), P.H.x1.data(), P.H.d0.data(), P.H.d1.data(), n, off[k], stage.data());
-            const double *rows[kRefineRows];
-            for (int r = 0; r < kRefineRows; ++r) rows[r] = d_data.p + refine_row(T, off[k], n, r);
-            PairData &D = Dh[k];
-            D.x0u = rows[0];
-            D.x0v = rows[1];
-            D.x1u = rows[2];
-            D.x1v = rows[3];
-            D.d0 = rows[4];
-            D.d1 = rows[5];
-            D.r0 = rows[6];
-            D.r1 = rows[7];
-            D.a0 = rows[8];
-            D.a1 = rows[9];
-            D.b0 = rows[10];
-            D.b1 = rows[11];
-            Ch[k] = P.C;
-            norm[k] = P.norm_scale;
-        }
-        for (int k = 0; k <= np; ++k) moff_run[k] = moff[k] - moff[0];
-        DevArray<PairData> d_D(np);
-        DevArray<PairConst> d_C(np);
-        DevArray<int64_t> d_list_off(np), d_moff(np + 1);
-        if (T > 0)
-            MP_HIP(hipMemcpyAsync(d_data.p, stage.data(), sizeof(double) * 6 * (size_t)T, hipMemcpyHostToDevice,
-                                  stream));
-        MP_HIP(hipMemcpyAsync(d_D.p, Dh.data(), sizeof(PairData) * np, hipMemcpyHostToDevice, stream));
-        MP_HIP(hipMemcpyAsync(d_C.p, Ch.data(), sizeof(PairConst) * np, hipMemcpyHostToDevice, stream));
-        MP_HIP(hipMemcpyAsync(d_list_off.p, list_off.data(), sizeof(int64_t) * np, hipMemcpyHostToDevice, stream));
-        MP_HIP(hipMemcpyAsync(d_moff.p, moff_run.data(), sizeof(int64_t) * (np + 1), hipMemcpyHostToDevice, stream));
-        if (v == kCal)
-            for (int k = 0; k < np; ++k) {
-                double *base = d_data.p;
-                const int64_t n = Ch[k].n;
-                auto row = [&](int r) { return base + refine_row(T, off[k], n, r); };
-                MP_HIP(launch_prep_pair(stream, Ch[k], Dh[k], row(6), row(7), row(8), row(9), row(10), row(11)));
-            }
-        stage_end(t0, tm.pairs_ms);
-
-        // the model of candidate m of the run in problem units, and its pair
-        auto problem_model = [&](int k, int64_t m) {
-            Model c = models[moff[0] + m];
-            if (variant == kSF || variant == kTF) {
-                c.focal0 /= norm[k];
-                c.focal1 /= norm[k];
-            }
-            return c;
-        };
-        // ---- the candidates' scores and counts, slab by slab ----
-        DevArray<double> d_scores((size_t)M);
-        DevArray<int> d_counts(3 * (size_t)M);
-        const std::vector<SelectSlab> slabs = select_slabs(M, model_chunk);
-        const size_t cap = slabs.empty() ? 0 : (size_t)(slabs[0].m1 - slabs[0].m0); // (the first is the largest)
-        const int nbuf = slabs.size() > 1 ? 2 : 1;
-        // (a work item holds at least one candidate: a slab has at most `cap` items)
-        std::unique_ptr<PinnedArray<ScoreRec>> h_recs[2];
-        std::unique_ptr<PinnedArray<SelectItem>> h_items[2];
-        std::unique_ptr<DevArray<ScoreRec>> d_recs[2];
-        std::unique_ptr<DevArray<SelectItem>> d_items[2];
-        std::unique_ptr<EventHolder> uploaded[2], scored[2];
-        for (int b = 0; b < nbuf && cap > 0; ++b) {
-            h_recs[b].reset(new PinnedArray<ScoreRec>(cap));
-            h_items[b].reset(new PinnedArray<SelectItem>(cap));
-            d_recs[b].reset(new DevArray<ScoreRec>(cap));
-            d_items[b].reset(new DevArray<SelectItem>(cap));
-            uploaded[b].reset(new EventHolder());
-            scored[b].reset(new EventHolder());
-        }
-        std::vector<SelectItem> items;
-        for (size_t si = 0; si < slabs.size(); ++si) {
-            const SelectSlab &s = slabs[si];
-            const int b = (int)(si % 2) % nbuf;
-            const int64_t ns = s.m1 - s.m0;
-            // (the host buffers' previous upload and the device buffers' previous launch are over)
-            if (si >= 2) {
-                MP_HIP(hipEventSynchronize(uploaded[b]->e));
-                MP_HIP(hipEventSynchronize(scored[b]->e));
-            }
-            t0 = Clock::now();
-            select_items(np, moff, s, tile, items);
-            std::memcpy(h_items[b]->p, items.data(), sizeof(SelectItem) * items.size());
-            ScoreRec *recs = h_recs[b]->p;
-            // candidates a .. e - 1 of the slab; the pair of each by a walk from the first one's
-            auto prepare = [&](int64_t a, int64_t e) {
-                int k = (int)(std::upper_bound(moff_run.begin(), moff_run.end(), s.m0 + a) - moff_run.begin()) - 1;
-                for (int64_t j = a; j < e; ++j) {
-                    const int64_t m = s.m0 + j;
-                    while (moff_run[k + 1] <= m) ++k;
-                    const Model c = problem_model(k, m);
-                    prepare_score_rec(Ch[k], c, recs[j]);
-                }
-            };
-            const int nthr = (int)std::min<int64_t>(kSelectPrepThreads, ns / kSelectPrepPerThread);
-            if (nthr <= 1) {
-                prepare(0, ns);
-            } else {
-                std::vector<std::thread> threads;
-                for (int t = 1; t < nthr; ++t) threads.emplace_back(prepare, ns * t / nthr, ns * (t + 1) / nthr);
-                prepare(0, ns / nthr);
-                for (auto &t : threads) t.join();
-            }
-            if (timed) tm.prepare_ms += 1e3 * secs(t0);
-            t0 = Clock::now();
-            MP_HIP(hipMemcpyAsync(d_recs[b]->p, recs, sizeof(ScoreRec) * (size_t)ns, hipMemcpyHostToDevice, stream));
-            MP_HIP(hipMemcpyAsync(d_items[b]->p, h_items[b]->p, sizeof(SelectItem) * items.size(),
-                                  hipMemcpyHostToDevice, stream));
-            MP_HIP(hipEventRecord(uploaded[b]->e, stream));
-            stage_end(t0, tm.upload_ms);
-            t0 = Clock::now();
-            MP_HIP(launch_select_score(stream, v, tile, d_D.p, d_C.p, d_items[b]->p, (int)items.size(), d_recs[b]->p,
-                                       s.m0, d_scores.p, d_counts.p));
-            MP_HIP(hipEventRecord(scored[b]->e, stream));
-            stage_end(t0, tm.score_ms);
-        }
-        // ---- the best candidate of every pair ----
-        t0 = Clock::now();
-        DevArray<SelectBest> d_best(np);
-        std::vector<SelectBest> best(np);
-        MP_HIP(launch_select_argmin(stream, d_moff.p, np, d_scores.p, d_best.p));
-        MP_HIP(hipMemcpyAsync(best.data(), d_best.p, sizeof(SelectBest) * np, hipMemcpyDeviceToHost, stream));
-        if (scores && M > 0)
-            MP_HIP(hipMemcpyAsync(scores + moff[0], d_scores.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost,
-                                  stream));
-        if (counts && M > 0)
-            MP_HIP(hipMemcpyAsync(counts + 3 * moff[0], d_counts.p, sizeof(int) * 3 * (size_t)M,
-                                  hipMemcpyDeviceToHost, stream));
-        MP_HIP(hipStreamSynchronize(stream));
-        if (timed) tm.argmin_ms += 1e3 * secs(t0);
-        // ---- the winners' lists: refine_batch's sweep, one item per pair with a winner ----
-        t0 = Clock::now();
-        std::vector<RefineItem> ritems;
-        std::vector<ScoreRec> rrecs;
-        std::vector<int> which;
-        for (int k = 0; k < np; ++k) {
-            SelectResult &R = results[run.p0 + k];
-            std::memset(&R, 0, sizeof(R));
-            R.best_score = DBL_MAX;
-            R.norm_scale = norm[k];
-            R.best_index = -1;
-            if (best[k].index < 0) continue;
-            if (best[k].index >= moff[k + 1] - moff[k]) throw std::runtime_error("select_argmin: index out of range");
-            RefineItem it;
-            it.pair = k;
-            it.buf = 0;
-            ritems.push_back(it);
-            rrecs.emplace_back();
-            prepare_score_rec(Ch[k], problem_model(k, moff_run[k] + best[k].index), rrecs.back());
-            which.push_back(k);
-        }
-        const size_t nw = which.size();
-        if (nw > 0) {
-            DevArray<RefineItem> d_ritems(nw);
-            DevArray<ScoreRec> d_rrecs(nw);
-            DevArray<RefineSweepOut> d_out(nw);
-            std::vector<RefineSweepOut> outs(nw);
-            MP_HIP(hipMemcpyAsync(d_ritems.p, ritems.data(), sizeof(RefineItem) * nw, hipMemcpyHostToDevice, stream));
-            MP_HIP(hipMemcpyAsync(d_rrecs.p, rrecs.data(), sizeof(ScoreRec) * nw, hipMemcpyHostToDevice, stream));
-            MP_HIP(launch_refine_sweep(stream, v, d_D.p, d_C.p, d_ritems.p, d_rrecs.p, (int)nw, d_list_off.p,
-                                       d_lists.p, 3 * T, d_out.p));
-            MP_HIP(hipMemcpyAsync(outs.data(), d_out.p, sizeof(RefineSweepOut) * nw, hipMemcpyDeviceToHost, stream));
-            MP_HIP(hipStreamSynchronize(stream));
-            for (size_t j = 0; j < nw; ++j) {
-                const int k = which[j];
-                SelectResult &R = results[run.p0 + k];
-                // (the same record through the same arithmetic: anything else is a defect; the
-                // measurement hook's other work-item sizes are not pinned to these bits)
-                if (tile == kSelectTile && std::memcmp(&outs[j].score, &best[k].score, sizeof(double)) != 0)
-                    throw std::runtime_error("select_batch: the winner's sweep score differs from its selected score");
-                R.best_score = best[k].score;
-                R.best_index = best[k].index;
-                for (int t = 0; t < 3; ++t) R.num_inliers[t] = outs[j].count[t];
-            }
-            if (inlier_idx && T > 0) {
-                std::vector<int> lists(3 * (size_t)T);
-                MP_HIP(hipMemcpyAsync(lists.data(), d_lists.p, sizeof(int) * lists.size(), hipMemcpyDeviceToHost,
-                                      stream));
-                MP_HIP(hipStreamSynchronize(stream));
-                for (int k : which) {
-                    const int32_t p = run.p0 + k;
-                    const int64_t n = Ch[k].n;
-                    for (int t = 0; t < 3; ++t)
-                        std::memcpy(inlier_idx + 3 * offsets[p] + t * n,
-                                    lists.data() + refine_list(T, off[k], n, 0, t),
-                                    sizeof(int) * (size_t)results[p].num_inliers[t]);
-                }
-            }
-        }
-        if (timed) tm.winners_ms += 1e3 * secs(t0);
-        MP_HIP(hipStreamSynchronize(stream));
+        ResidentPairs R(stream, variant, np, offsets + run.p0, x0, x1, d0, d1, nullptr, cam0 + (size_t)nc * run.p0,
+                        cam1 + (size_t)nc * run.p0, opts, cfg);
+        if (timed) tm.pairs_ms += 1e3 * secs(t0);
+        select_run(R, stream, PairSel{np, nullptr}, offsets + run.p0, model_offsets + run.p0, models, scores, counts,
+                   results + run.p0, inlier_idx, model_chunk, tile, timed, tm);
     }
     if (timed) {
         std::lock_guard<std::mutex> lk(g_select_mu);
@@ -3058,12 +3023,160 @@ HypTiming hypothesize_timing_last() {
     return g_hyp_timing;
 }
 
+namespace {
+// what mp_hypothesize_batch and mp_hypothesize_set run on: variants 0 .. 2, use_shift on,
+// the default MD solvers
+void check_hyp_supported(int variant, const RansacOptions &opts, const EstimatorConfig &cfg) {
+    if (variant == kScaleOnly)
+        throw std::invalid_argument("hypothesize_batch does not support MP_SCALE_ONLY (variant 3)");
+    if (variant < 0 || variant > 2)
+        throw std::invalid_argument("variant must be 0 (calibrated), 1 (shared focal) or 2 (two focal)");
+    if (!cfg.use_shift) throw std::invalid_argument("hypothesize_batch does not support use_shift = 0");
+    if (opts.use_ours || opts.use_4p4d)
+        throw std::invalid_argument("hypothesize_batch does not support the alternate MD solvers (use_ours / use_4p4d)");
+}
+// the samples of ne entries (pairs of a call, or of a selection): entry e has n(e)
+// correspondences and the samples sample_offsets[e] .. sample_offsets[e + 1] - 1.  Types,
+// ranges and repeats; a kernel only ever reads indices that passed here.
+template <class N>
+void check_hyp_samples(int v, int32_t ne, N n_of, const int64_t *sample_offsets, const int32_t *sample_types,
+                       const int32_t *sample_idx) {
+    const int ksz[2] = {v == kCal ? 3 : 4, v == kCal ? 5 : (v == kSF ? 6 : 7)};
+    static_assert(kSampleStride == 8, "a sample has 8 index slots (mp_hypothesize_batch)");
+    for (int32_t p = 0; p < ne; ++p) {
+        const int64_t n = n_of(p);
+        for (int64_t s = sample_offsets[p]; s < sample_offsets[p + 1]; ++s) {
+            const int32_t t = sample_types[s];
+            if (t != 0 && t != 1)
+                throw std::invalid_argument("sample " + std::to_string(s) + ": type must be 0 (MD solver) or 1 (point solver)");
+            const int k = ksz[t];
+            if (n < k)
+                throw std::invalid_argument("sample " + std::to_string(s) + ": pair " + std::to_string(p) +
+                                            " has too few correspondences for the solver");
+            const int32_t *q = sample_idx + kSampleStride * s;
+            for (int a = 0; a < k; ++a) {
+                if (q[a] < 0 || q[a] >= n)
+                    throw std::invalid_argument("sample " + std::to_string(s) + ": index outside the pair");
+                for (int b = 0; b < a; ++b)
+                    if (q[a] == q[b])
+                        throw std::invalid_argument("sample " + std::to_string(s) + ": repeated index");
+            }
+        }
+    }
+}
+
+// one slab's device and host buffers, sized for the largest slab of a call of S_all samples
+struct HypBuffers {
+    int64_t slab_cap;
+    DevArray<int> d_samples, d_list, d_counts;
+    DevArray<HypItem> d_items;
+    DevArray<Model> d_models;
+    DevArray<double> d_cand, d_pen;
+    DevArray<int> d_ncand, d_valid;
+    DevArray<Model> d_slots;
+    PtWorkspace W;
+    std::vector<int> h_samples, h_list;
+    std::vector<HypItem> h_items;
+    HypPlan plan;
+    HypBuffers(int v, int64_t S_all, int64_t sample_chunk)
+        : slab_cap(std::min<int64_t>(S_all, hyp_slabs(S_all, sample_chunk)[0].s1)),
+          d_samples((size_t)slab_cap * kSampleStride), d_list((size_t)slab_cap), d_counts((size_t)slab_cap),
+          d_items((size_t)slab_cap), d_models((size_t)slab_cap * max_models(v)),
+          d_cand((size_t)slab_cap * kPtCandStride), d_pen(v == kSF ? (size_t)slab_cap * kPtPenStride : 1),
+          d_ncand((size_t)slab_cap), d_valid((size_t)slab_cap * kPtSlotStride),
+          d_slots((size_t)slab_cap * kPtSlotStride), W{d_cand.p, d_ncand.p, d_slots.p, d_valid.p, d_pen.p},
+          h_samples((size_t)slab_cap * kSampleStride), h_list((size_t)slab_cap), h_items((size_t)slab_cap) {}
+};
+
+// The sample models of the selected resident pairs (the body of mp_hypothesize_batch and
+// mp_hypothesize_set), S = soff[ns] - soff[0] > 0 samples, checked by check_hyp_samples.
+// soff: ns + 1 offsets into sample_types / sample_idx / counts (models: max_models slots per
+// sample); the run's samples go through the device in slabs (host/hypothesis_plan.h), one
+// launch_hyp_solve each.
+void hypothesize_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const int64_t *soff,
+                     const int32_t *sample_types, const int32_t *sample_idx, Model *models, int32_t *counts,
+                     int64_t sample_chunk, HypBuffers &B, bool timed, HypTiming &tm) {
+    const int ns_sel = sel.n;
+    const int v = R.v;
+    const int ksz[2] = {v == kCal ? 3 : 4, v == kCal ? 5 : (v == kSF ? 6 : 7)};
+    const int maxm = max_models(v);
+    const int cap[2] = {hyp_md_cap(v), hyp_pt_cap(v)};
+    const int64_t S = soff[ns_sel] - soff[0];
+    auto stage_end = [&](Clock::time_point t0, double &ms) {
+        if (!timed) return;
+        MP_HIP(hipStreamSynchronize(stream));
+        ms += 1e3 * secs(t0);
+    };
+    HypPlan &plan = B.plan;
+    for (const HypSlab &s : hyp_slabs(S, sample_chunk)) {
+        const int64_t ns = s.s1 - s.s0;
+        const int64_t g0 = soff[0] + s.s0; // the slab's first sample in the caller's arrays
+        Clock::time_point t0 = Clock::now();
+        hyp_items(ns_sel, soff, sample_types + soff[0], s, cap, plan);
+        const size_t nl[2] = {plan.list[0].size(), plan.list[1].size()};
+        const size_t ni[2] = {plan.items[0].size(), plan.items[1].size()};
+        if ((int64_t)(nl[0] + nl[1]) != ns || (int64_t)(ni[0] + ni[1]) > ns)
+            throw std::logic_error("hypothesize_batch: the slab's lists do not cover its samples");
+        // (only the slots a solver reads, range-checked before, reach the device)
+        for (int64_t b = 0; b < ns; ++b) {
+            const int k = ksz[sample_types[g0 + b] != 0 ? 1 : 0];
+            const int32_t *q = sample_idx + kSampleStride * (g0 + b);
+            int *o = B.h_samples.data() + kSampleStride * b;
+            for (int a = 0; a < kSampleStride; ++a) o[a] = a < k ? q[a] : 0;
+        }
+        std::copy(plan.list[0].begin(), plan.list[0].end(), B.h_list.begin());
+        std::copy(plan.list[1].begin(), plan.list[1].end(), B.h_list.begin() + nl[0]);
+        std::copy(plan.items[0].begin(), plan.items[0].end(), B.h_items.begin());
+        std::copy(plan.items[1].begin(), plan.items[1].end(), B.h_items.begin() + ni[0]);
+        // (the plan names the selection's entries; the kernels index the resident records)
+        if (sel.ids)
+            for (size_t i = 0; i < ni[0] + ni[1]; ++i) B.h_items[i].pair = sel.ids[B.h_items[i].pair];
+        if (timed) tm.plan_ms += 1e3 * secs(t0);
+        t0 = Clock::now();
+        MP_HIP(hipMemcpyAsync(B.d_samples.p, B.h_samples.data(), sizeof(int) * kSampleStride * (size_t)ns,
+                              hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(B.d_list.p, B.h_list.data(), sizeof(int) * (size_t)ns, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(B.d_items.p, B.h_items.data(), sizeof(HypItem) * (ni[0] + ni[1]), hipMemcpyHostToDevice,
+                              stream));
+        MP_HIP(hipMemsetAsync(B.d_models.p, 0, sizeof(Model) * (size_t)ns * maxm, stream));
+        MP_HIP(hipMemsetAsync(B.d_counts.p, 0, sizeof(int) * (size_t)ns, stream));
+        stage_end(t0, tm.upload_ms);
+        t0 = Clock::now();
+        MP_HIP(launch_hyp_solve(stream, v, R.d_D.p, R.d_C.p, B.d_items.p, (int)ni[0], B.d_list.p, B.d_items.p + ni[0],
+                                (int)ni[1], B.d_list.p + nl[0], (int)nl[1], B.d_samples.p, B.W, B.d_models.p,
+                                B.d_counts.p));
+        stage_end(t0, tm.solve_ms);
+        t0 = Clock::now();
+        Model *out = models + (size_t)g0 * maxm;
+        MP_HIP(hipMemcpyAsync(out, B.d_models.p, sizeof(Model) * (size_t)ns * maxm, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipMemcpyAsync(counts + g0, B.d_counts.p, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, stream));
+        // (the host buffers are rewritten for the next slab, the device ones by its launches)
+        MP_HIP(hipStreamSynchronize(stream));
+        // user units: the focals times the pair's normalisation scale (one product each)
+        if (v != kCal) {
+            int j = (int)(std::upper_bound(soff, soff + ns_sel + 1, g0) - soff) - 1;
+            for (int64_t b = 0; b < ns; ++b) {
+                while (soff[j + 1] <= g0 + b) ++j;
+                const double norm = R.norm_scale[sel[j]];
+                const int cnt = counts[g0 + b];
+                if (cnt < 0 || cnt > maxm) throw std::runtime_error("hypothesize_batch: model count out of range");
+                for (int i = 0; i < cnt; ++i) {
+                    Model &m = out[(size_t)b * maxm + i];
+                    m.focal0 *= norm;
+                    m.focal1 *= norm;
+                }
+            }
+        }
+        if (timed) tm.download_ms += 1e3 * secs(t0);
+    }
+}
+} // namespace
+
 // The estimators' sample models over many pairs (mp_hypothesize_batch).  Every argument is
 // checked on the host before the device is touched: a kernel only ever reads indices that
 // were range-checked here, from a copy in which the unused slots of a sample are zero.  The
-// pairs of a run (host/refine_plan.h) are resident at once, set up as refine_batch /
-// select_batch set theirs up; the run's samples go through the device in slabs
-// (host/hypothesis_plan.h), one launch_hyp_solve each.
+// pairs of a run (host/refine_plan.h) are resident at once (host/resident_pairs.h, as
+// refine_batch's and select_batch's); the run's samples go through hypothesize_run.
 void hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
                        const double *d0, const double *d1, const double *min_depth, const double *cam0,
                        const double *cam1, const RansacOptions &opts, const EstimatorConfig &cfg,
@@ -3077,9 +3190,7 @@ void hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, c
     if (num_pairs < 0) throw std::invalid_argument("negative pair count");
     if (chunk < 0) throw std::invalid_argument("chunk must not be negative");
     if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
-    if (!cfg.use_shift) throw std::invalid_argument("hypothesize_batch does not support use_shift = 0");
-    if (opts.use_ours || opts.use_4p4d)
-        throw std::invalid_argument("hypothesize_batch does not support the alternate MD solvers (use_ours / use_4p4d)");
+    check_hyp_supported(variant, opts, cfg);
     {
         PairInput none; // (the option checks of every entry point)
         validate(none, opts);
@@ -3099,32 +3210,10 @@ void hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, c
     if (S_all > 0 && (!sample_types || !sample_idx || !models || !counts))
         throw std::invalid_argument("null sample_types, sample_idx, models or counts");
     const int v = variant;
-    const int ksz[2] = {v == kCal ? 3 : 4, v == kCal ? 5 : (v == kSF ? 6 : 7)};
-    static_assert(kSampleStride == 8, "a sample has 8 index slots (mp_hypothesize_batch)");
-    for (int32_t p = 0; p < num_pairs; ++p) {
-        const int64_t n = offsets[p + 1] - offsets[p];
-        for (int64_t s = sample_offsets[p]; s < sample_offsets[p + 1]; ++s) {
-            const int32_t t = sample_types[s];
-            if (t != 0 && t != 1)
-                throw std::invalid_argument("sample " + std::to_string(s) + ": type must be 0 (MD solver) or 1 (point solver)");
-            const int k = ksz[t];
-            if (n < k)
-                throw std::invalid_argument("sample " + std::to_string(s) + ": pair " + std::to_string(p) +
-                                            " has too few correspondences for the solver");
-            const int32_t *q = sample_idx + kSampleStride * s;
-            for (int a = 0; a < k; ++a) {
-                if (q[a] < 0 || q[a] >= n)
-                    throw std::invalid_argument("sample " + std::to_string(s) + ": index outside the pair");
-                for (int b = 0; b < a; ++b)
-                    if (q[a] == q[b])
-                        throw std::invalid_argument("sample " + std::to_string(s) + ": repeated index");
-            }
-        }
-    }
+    check_hyp_samples(v, num_pairs, [&](int32_t p) { return offsets[p + 1] - offsets[p]; }, sample_offsets,
+                      sample_types, sample_idx);
 
     const int nc = v == kCal ? 9 : 2;
-    const int maxm = max_models(v);
-    const int cap[2] = {hyp_md_cap(v), hyp_pt_cap(v)};
     auto pair_input = [&](int32_t p) {
         const int64_t o = offsets[p];
         PairInput in;
@@ -3150,144 +3239,233 @@ void hypothesize_batch(int variant, int32_t num_pairs, const int64_t *offsets, c
     HypTiming tm;
     CtxLease lease(device);
     hipStream_t stream = lease.c->stream;
-    auto stage_end = [&](Clock::time_point t0, double &ms) {
-        if (!timed) return;
-        MP_HIP(hipStreamSynchronize(stream));
-        ms += 1e3 * secs(t0);
-    };
-    // one slab's device buffers, sized for the largest slab of the call
-    const int64_t slab_cap = std::min<int64_t>(S_all, hyp_slabs(S_all, sample_chunk)[0].s1);
-    DevArray<int> d_samples((size_t)slab_cap * kSampleStride), d_list((size_t)slab_cap), d_counts((size_t)slab_cap);
-    DevArray<HypItem> d_items((size_t)slab_cap);
-    DevArray<Model> d_models((size_t)slab_cap * maxm);
-    DevArray<double> d_cand((size_t)slab_cap * kPtCandStride), d_pen(v == kSF ? (size_t)slab_cap * kPtPenStride : 1);
-    DevArray<int> d_ncand((size_t)slab_cap), d_valid((size_t)slab_cap * kPtSlotStride);
-    DevArray<Model> d_slots((size_t)slab_cap * kPtSlotStride);
-    const PtWorkspace W{d_cand.p, d_ncand.p, d_slots.p, d_valid.p, d_pen.p};
-    std::vector<int> h_samples((size_t)slab_cap * kSampleStride), h_list((size_t)slab_cap);
-    std::vector<HypItem> h_items((size_t)slab_cap);
-    HypPlan plan;
+    HypBuffers B(v, S_all, sample_chunk);
 
     for (const RefineRun &run : refine_plan(num_pairs, offsets, chunk)) {
         const int np = run.p1 - run.p0;
-        const int64_t T = run.total;
         const int64_t *soff = sample_offsets + run.p0; // np + 1 values; sample 0 of the run at soff[0]
-        const int64_t S = soff[np] - soff[0];
-        if (S == 0) {
+        if (soff[np] - soff[0] == 0) {
             if (norm_scale)
                 for (int k = 0; k < np; ++k)
                     norm_scale[run.p0 + k] = make_problem(pair_input(run.p0 + k), opts, cfg).norm_scale;
             continue;
         }
-        // ---- problems, packed upload, pair records (as refine_batch / select_batch) ----
+        // ---- problems, packed upload, pair records (host/resident_pairs.h) ----
         Clock::time_point t0 = Clock::now();
-        std::vector<double> norm(np);
-        std::vector<PairData> Dh(np);
-        std::vector<PairConst> Ch(np);
-        std::vector<int64_t> off(np);
-        std::vector<double> stage(6 * (size_t)T);
-        DevArray<double> d_data((size_t)kRefineRows * T);
-        for (int k = 0; k < np; ++k) {
-            const int32_t p = run.p0 + k;
-            const int64_t n = offsets[p + 1] - offsets[p];
-            const Problem P = make_problem(pair_input(p), opts, cfg);
-            off[k] = offsets[p] - offsets[run.p0];
-            refine_pack_pair(P.H.x0.data(), P.H.x1.data(), P.H.d0.data(), P.H.d1.data(), n, off[k], stage.data());
-            const double *rows[kRefineRows];
-            for (int r = 0; r < kRefineRows; ++r) rows[r] = d_data.p + refine_row(T, off[k], n, r);
-            PairData &D = Dh[k];
-            D.x0u = rows[0];
-            D.x0v = rows[1];
-            D.x1u = rows[2];
-            D.x1v = rows[3];
-            D.d0 = rows[4];
-            D.d1 = rows[5];
-            D.r0 = rows[6];
-            D.r1 = rows[7];
-            D.a0 = rows[8];
-            D.a1 = rows[9];
-            D.b0 = rows[10];
-            D.b1 = rows[11];
-            Ch[k] = P.C;
-            norm[k] = P.norm_scale;
-            if (norm_scale) norm_scale[p] = P.norm_scale;
-        }
-        DevArray<PairData> d_D(np);
-        DevArray<PairConst> d_C(np);
-        if (T > 0)
-            MP_HIP(hipMemcpyAsync(d_data.p, stage.data(), sizeof(double) * 6 * (size_t)T, hipMemcpyHostToDevice,
-                                  stream));
-        MP_HIP(hipMemcpyAsync(d_D.p, Dh.data(), sizeof(PairData) * np, hipMemcpyHostToDevice, stream));
-        MP_HIP(hipMemcpyAsync(d_C.p, Ch.data(), sizeof(PairConst) * np, hipMemcpyHostToDevice, stream));
-        if (v == kCal)
-            for (int k = 0; k < np; ++k) {
-                double *base = d_data.p;
-                const int64_t n = Ch[k].n;
-                auto row = [&](int r) { return base + refine_row(T, off[k], n, r); };
-                MP_HIP(launch_prep_pair(stream, Ch[k], Dh[k], row(6), row(7), row(8), row(9), row(10), row(11)));
-            }
-        stage_end(t0, tm.pairs_ms);
-
-        // ---- the samples, slab by slab ----
-        for (const HypSlab &s : hyp_slabs(S, sample_chunk)) {
-            const int64_t ns = s.s1 - s.s0;
-            const int64_t g0 = soff[0] + s.s0; // the slab's first sample in the caller's arrays
-            t0 = Clock::now();
-            hyp_items(np, soff, sample_types + soff[0], s, cap, plan);
-            const size_t nl[2] = {plan.list[0].size(), plan.list[1].size()};
-            const size_t ni[2] = {plan.items[0].size(), plan.items[1].size()};
-            if ((int64_t)(nl[0] + nl[1]) != ns || (int64_t)(ni[0] + ni[1]) > ns)
-                throw std::logic_error("hypothesize_batch: the slab's lists do not cover its samples");
-            // (only the slots a solver reads, range-checked above, reach the device)
-            for (int64_t b = 0; b < ns; ++b) {
-                const int k = ksz[sample_types[g0 + b] != 0 ? 1 : 0];
-                const int32_t *q = sample_idx + kSampleStride * (g0 + b);
-                int *o = h_samples.data() + kSampleStride * b;
-                for (int a = 0; a < kSampleStride; ++a) o[a] = a < k ? q[a] : 0;
-            }
-            std::copy(plan.list[0].begin(), plan.list[0].end(), h_list.begin());
-            std::copy(plan.list[1].begin(), plan.list[1].end(), h_list.begin() + nl[0]);
-            std::copy(plan.items[0].begin(), plan.items[0].end(), h_items.begin());
-            std::copy(plan.items[1].begin(), plan.items[1].end(), h_items.begin() + ni[0]);
-            if (timed) tm.plan_ms += 1e3 * secs(t0);
-            t0 = Clock::now();
-            MP_HIP(hipMemcpyAsync(d_samples.p, h_samples.data(), sizeof(int) * kSampleStride * (size_t)ns,
-                                  hipMemcpyHostToDevice, stream));
-            MP_HIP(hipMemcpyAsync(d_list.p, h_list.data(), sizeof(int) * (size_t)ns, hipMemcpyHostToDevice, stream));
-            MP_HIP(hipMemcpyAsync(d_items.p, h_items.data(), sizeof(HypItem) * (ni[0] + ni[1]), hipMemcpyHostToDevice,
-                                  stream));
-            MP_HIP(hipMemsetAsync(d_models.p, 0, sizeof(Model) * (size_t)ns * maxm, stream));
-            MP_HIP(hipMemsetAsync(d_counts.p, 0, sizeof(int) * (size_t)ns, stream));
-            stage_end(t0, tm.upload_ms);
-            t0 = Clock::now();
-            MP_HIP(launch_hyp_solve(stream, v, d_D.p, d_C.p, d_items.p, (int)ni[0], d_list.p, d_items.p + ni[0],
-                                    (int)ni[1], d_list.p + nl[0], (int)nl[1], d_samples.p, W, d_models.p, d_counts.p));
-            stage_end(t0, tm.solve_ms);
-            t0 = Clock::now();
-            Model *out = models + (size_t)g0 * maxm;
-            MP_HIP(hipMemcpyAsync(out, d_models.p, sizeof(Model) * (size_t)ns * maxm, hipMemcpyDeviceToHost, stream));
-            MP_HIP(hipMemcpyAsync(counts + g0, d_counts.p, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, stream));
-            // (the host buffers are rewritten for the next slab, the device ones by its launches)
-            MP_HIP(hipStreamSynchronize(stream));
-            // user units: the focals times the pair's normalisation scale (one product each)
-            if (v != kCal) {
-                int k = (int)(std::upper_bound(soff, soff + np + 1, g0) - soff) - 1;
-                for (int64_t b = 0; b < ns; ++b) {
-                    while (soff[k + 1] <= g0 + b) ++k;
-                    const int cnt = counts[g0 + b];
-                    if (cnt < 0 || cnt > maxm) throw std::runtime_error("hypothesize_batch: model count out of range");
-                    for (int j = 0; j < cnt; ++j) {
-                        Model &m = out[(size_t)b * maxm + j];
-                        m.focal0 *= norm[k];
-                        m.focal1 *= norm[k];
-                    }
-                }
-            }
-            if (timed) tm.download_ms += 1e3 * secs(t0);
-        }
+        ResidentPairs R(stream, variant, np, offsets + run.p0, x0, x1, d0, d1, min_depth + 2 * (size_t)run.p0,
+                        cam0 + (size_t)nc * run.p0, cam1 + (size_t)nc * run.p0, opts, cfg);
+        if (norm_scale) std::copy(R.norm_scale.begin(), R.norm_scale.end(), norm_scale + run.p0);
+        if (timed) tm.pairs_ms += 1e3 * secs(t0);
+        hypothesize_run(R, stream, PairSel{np, nullptr}, soff, sample_types, sample_idx, models, counts, sample_chunk,
+                        B, timed, tm);
     }
     if (timed) {
         std::lock_guard<std::mutex> lk(g_hyp_mu);
+        g_hyp_timing = tm;
+    }
+}
+
+// ---- the pair set (mp_pair_set_*): pairs set up once, resident until destroyed ----
+struct PairSet {
+    std::mutex mu; // calls on one set are serialised
+    int device = 0;
+    int variant = 0;
+    RansacOptions opts;
+    EstimatorConfig cfg;
+    std::unique_ptr<ResidentPairs> R; // null: an empty set (no pairs)
+    int32_t num_pairs = 0;
+    std::vector<char> seen;        // check_selection's scratch
+    std::vector<int64_t> out_off;  // the selection's positions in inlier_idx
+    // the selection of a call, checked; out_off[j]: the correspondences of the entries before j
+    PairSel select(int32_t num_sel, const int32_t *pair_ids) {
+        check_selection(num_pairs, num_sel, pair_ids, seen);
+        out_off.assign((size_t)num_sel + 1, 0);
+        for (int32_t j = 0; j < num_sel; ++j) out_off[j + 1] = out_off[j] + R->n[pair_ids ? pair_ids[j] : j];
+        return PairSel{num_sel, pair_ids};
+    }
+};
+
+namespace {
+void release_live_sets() {
+    std::vector<PairSet *> sets;
+    {
+        std::lock_guard<std::mutex> lk(g_sets_mu);
+        sets.swap(g_sets);
+    }
+    for (PairSet *s : sets) delete s;
+}
+} // namespace
+
+int pair_set_prep_mode(int mode) {
+    if (mode != 0 && mode != 1)
+        throw std::invalid_argument("mode must be 0 (one preparation launch) or 1 (one launch per pair)");
+    return g_pair_set_prep.exchange(mode);
+}
+
+PairSet *pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                         const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                         const double *cam1, const RansacOptions &opts, const EstimatorConfig &cfg, int device) {
+    if (variant < 0 || variant > 3)
+        throw std::invalid_argument("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)");
+    if (num_pairs < 0) throw std::invalid_argument("negative pair count");
+    {
+        PairInput none; // (the option checks of every entry point)
+        validate(none, opts);
+    }
+    if (num_pairs > 0) {
+        if (!offsets || !min_depth || !cam0 || !cam1)
+            throw std::invalid_argument("null offsets, min_depth or cameras");
+        check_pair_arrays(variant, num_pairs, offsets, x0, x1, d0, d1);
+        if (offsets[num_pairs] - offsets[0] > kPairSetMaxCorr)
+            throw std::invalid_argument("more than 2^26 correspondences in one set");
+    }
+    std::unique_ptr<PairSet> S(new PairSet());
+    S->device = device;
+    S->variant = variant;
+    S->opts = opts;
+    S->cfg = cfg;
+    S->num_pairs = num_pairs;
+    if (num_pairs > 0) {
+        CtxLease lease(device);
+        S->R.reset(new ResidentPairs(lease.c->stream, variant, num_pairs, offsets, x0, x1, d0, d1, min_depth, cam0,
+                                     cam1, opts, cfg));
+    }
+    std::lock_guard<std::mutex> lk(g_sets_mu);
+    g_sets.push_back(S.get());
+    return S.release();
+}
+
+void pair_set_destroy(PairSet *set) {
+    if (!set) return;
+    {
+        std::lock_guard<std::mutex> lk(g_sets_mu);
+        auto it = std::find(g_sets.begin(), g_sets.end(), set);
+        if (it == g_sets.end()) throw std::invalid_argument("not a live pair set");
+        g_sets.erase(it);
+    }
+    { std::lock_guard<std::mutex> lk(set->mu); } // (a call still running on it ends first)
+    delete set;
+}
+
+void pair_set_info(const PairSet *set, int32_t *variant, int32_t *num_pairs, int64_t *correspondences,
+                   int64_t *resident_bytes, int32_t *device) {
+    if (!set) throw std::invalid_argument("null pair set");
+    std::lock_guard<std::mutex> lk(const_cast<PairSet *>(set)->mu);
+    if (variant) *variant = set->variant;
+    if (num_pairs) *num_pairs = set->num_pairs;
+    if (correspondences) *correspondences = set->R ? set->R->T : 0;
+    if (resident_bytes) *resident_bytes = set->R ? set->R->resident_bytes() : 0;
+    if (device) *device = set->device;
+}
+
+void pair_set_norm_scales(const PairSet *set, double *out) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (set->num_pairs == 0) return;
+    if (!out) throw std::invalid_argument("null output");
+    std::copy(set->R->norm_scale.begin(), set->R->norm_scale.end(), out);
+}
+
+void pair_set_rows(const PairSet *set, int32_t pair, double *out) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (pair < 0 || pair >= set->num_pairs) throw std::invalid_argument("pair outside the set");
+    std::lock_guard<std::mutex> lk(const_cast<PairSet *>(set)->mu);
+    const ResidentPairs &R = *set->R;
+    const int64_t n = R.n[pair];
+    if (n == 0) return;
+    if (!out) throw std::invalid_argument("null output");
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+    // rows 0 .. 5 and 6 .. 11 of a pair are each contiguous (host/refine_plan.h refine_row)
+    MP_HIP(hipMemcpyAsync(out, R.d_data.p + refine_row(R.T, R.off[pair], n, 0), sizeof(double) * 6 * (size_t)n,
+                          hipMemcpyDeviceToHost, stream));
+    MP_HIP(hipMemcpyAsync(out + 6 * n, R.d_data.p + refine_row(R.T, R.off[pair], n, 6), sizeof(double) * 6 * (size_t)n,
+                          hipMemcpyDeviceToHost, stream));
+    MP_HIP(hipStreamSynchronize(stream));
+}
+
+void refine_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int rounds, Model *models,
+                RefineResult *results, int32_t *inlier_idx) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (rounds < 1 || rounds > 64) throw std::invalid_argument("rounds must be in 1..64");
+    std::lock_guard<std::mutex> lk(set->mu);
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        return;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    if (num_sel == 0) return;
+    if (!models || !results) throw std::invalid_argument("null models or results");
+    CtxLease lease(set->device);
+    refine_run(*set->R, lease.c->stream, sel, set->out_off.data(), set->cfg, rounds, models, results, inlier_idx);
+}
+
+void select_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
+                const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
+                int64_t model_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (model_chunk < 0) throw std::invalid_argument("model_chunk must not be negative");
+    std::lock_guard<std::mutex> lk(set->mu);
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        return;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    if (num_sel == 0) return;
+    if (!model_offsets || !results) throw std::invalid_argument("null model_offsets or results");
+    if (model_offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+    for (int32_t j = 0; j < num_sel; ++j)
+        if (model_offsets[j + 1] < model_offsets[j]) throw std::invalid_argument("offsets must not decrease");
+    if (model_offsets[num_sel] - model_offsets[0] > kSelectModelsMax)
+        throw std::invalid_argument("more than 2^28 candidates");
+    if (model_offsets[num_sel] > model_offsets[0] && !models) throw std::invalid_argument("null models");
+    const int tile_set = g_select_tile.load();
+    const int tile = tile_set ? tile_set : kSelectTile;
+    const bool timed = g_prof_on.load();
+    SelectTiming tm;
+    CtxLease lease(set->device);
+    select_run(*set->R, lease.c->stream, sel, set->out_off.data(), model_offsets, models, scores, counts, results,
+               inlier_idx, model_chunk, tile, timed, tm);
+    if (timed) {
+        std::lock_guard<std::mutex> lk2(g_select_mu);
+        g_select_timing = tm;
+    }
+}
+
+void hypothesize_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                     const int32_t *sample_types, const int32_t *sample_idx, Model *models, int32_t *counts,
+                     int64_t sample_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_hyp_supported(set->variant, set->opts, set->cfg);
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        return;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    if (num_sel == 0) return;
+    if (!sample_offsets) throw std::invalid_argument("null sample_offsets");
+    if (sample_offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+    for (int32_t j = 0; j < num_sel; ++j)
+        if (sample_offsets[j + 1] < sample_offsets[j]) throw std::invalid_argument("offsets must not decrease");
+    const int64_t S = sample_offsets[num_sel] - sample_offsets[0];
+    if (S > kHypSamplesMax) throw std::invalid_argument("more than 2^22 samples");
+    if (S == 0) return;
+    if (!sample_types || !sample_idx || !models || !counts)
+        throw std::invalid_argument("null sample_types, sample_idx, models or counts");
+    const ResidentPairs &R = *set->R;
+    check_hyp_samples(R.v, num_sel, [&](int32_t j) { return R.n[sel[j]]; }, sample_offsets, sample_types, sample_idx);
+    const bool timed = g_prof_on.load();
+    HypTiming tm;
+    CtxLease lease(set->device);
+    HypBuffers B(R.v, S, sample_chunk);
+    hypothesize_run(*set->R, lease.c->stream, sel, sample_offsets, sample_types, sample_idx, models, counts,
+                    sample_chunk, B, timed, tm);
+    if (timed) {
+        std::lock_guard<std::mutex> lk2(g_hyp_mu);
         g_hyp_timing = tm;
     }
 }

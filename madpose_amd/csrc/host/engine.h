@@ -181,6 +181,46 @@ struct HypTiming {
 };
 HypTiming hypothesize_timing_last();
 
+// Pairs set up once and resident on one device until destroyed (mp_pair_set_*;
+// host/resident_pairs.h): the setup refine_batch / select_batch / hypothesize_batch make per
+// call -- make_problem, the packed upload, the pair records, the calibrated preparation --
+// under the options and config given at creation.  All pairs are one resident range
+// (at most host/pair_set_plan.h kPairSetMaxCorr correspondences).  refine_set / select_set /
+// hypothesize_set run the batch entries' stage bodies on a selection of the set's pairs
+// (pair_ids: num_sel distinct indices in any order, or null with num_sel = the pair count:
+// all in order) and return the bytes the batch entry returns on those pairs' inputs in that
+// order; per-pair arguments and results are indexed by position in the selection, and
+// inlier_idx is the batch layout over the selected pairs.  A call leaves nothing in the set
+// that a later call can see.  Calls on one set are serialised by its mutex; a context is
+// leased per call.  Sets still live at process teardown are released before the pooled
+// contexts go.  hypothesize_set: std::invalid_argument on a set whose variant or options
+// hypothesize_batch rejects.
+struct PairSet;
+PairSet *pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
+                         const double *d0, const double *d1, const double *min_depth, const double *cam0,
+                         const double *cam1, const RansacOptions &opts, const EstimatorConfig &cfg, int device);
+void pair_set_destroy(PairSet *set); // null: nothing
+// resident_bytes: the rows (96 bytes per correspondence) and the list buffers allocated so
+// far (12 bytes per correspondence each: none after creation or hypothesize_set, one after
+// select_set, two after refine_set); the per-pair records are not counted
+void pair_set_info(const PairSet *set, int32_t *variant, int32_t *num_pairs, int64_t *correspondences,
+                   int64_t *resident_bytes, int32_t *device);
+void pair_set_norm_scales(const PairSet *set, double *out);
+void refine_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int rounds, Model *models,
+                RefineResult *results, int32_t *inlier_idx);
+void select_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
+                const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
+                int64_t model_chunk);
+void hypothesize_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                     const int32_t *sample_types, const int32_t *sample_idx, Model *models, int32_t *counts,
+                     int64_t sample_chunk);
+// Test and measurement hooks (mp_debug_pair_set_prep, mp_debug_pair_set_rows).
+// pair_set_prep_mode: how the following setups (sets and batch entries, process-wide) derive
+// the calibrated rows: 0 one launch_prep_pairs, 1 one launch_prep_pair per pair; returns the
+// previous mode.  pair_set_rows: rows 0 .. 11 of a pair (12 n doubles).
+int pair_set_prep_mode(int mode);
+void pair_set_rows(const PairSet *set, int32_t pair, double *out);
+
 // Standalone solvers on the device (mp_solve_* / mp_relpose_5pt).
 // alt: 0 default MD solver, 1 use_ours, 2 use_4p4d (two-focal)
 int solve_md_direct(int variant, const double *x, const double *y, const double *dx, const double *dy, double *sols,

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../host/pair_set_plan.h"
 #include "../include/mp_types.h"
 
 namespace mp {
@@ -12,6 +13,12 @@ constexpr int kSampleStride = 8; // sample indices per iteration slot (max minim
 // the rays' first two components, a = K0^-1 x0 and b = K1^-1 x1 (PairData::a0 .. b1)
 hipError_t launch_prep_pair(hipStream_t s, const PairConst &C, const PairData &D, double *r0, double *r1,
                             double *a0 = nullptr, double *a1 = nullptr, double *b0 = nullptr, double *b1 = nullptr);
+
+// launch_prep_pair for many resident calibrated pairs in one launch: one workgroup per
+// item (host/pair_set_plan.h), rows 6 .. 11 of every listed pair (Ds[k].r0 .. b1) written
+// with launch_prep_pair's bits.  Ds / Cs / items: device arrays.
+hipError_t launch_prep_pairs(hipStream_t s, const PairData *Ds, const PairConst *Cs, const PrepItem *items,
+                             int nitems);
 
 // MD minimal solver over the listed iterations (md_exact: R lanes per sample).
 hipError_t launch_md_solve(hipStream_t s, const PairData &D, const PairConst &C, const int *list, int nlist,

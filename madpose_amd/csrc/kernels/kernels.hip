@@ -108,6 +108,47 @@ __global__ void prep_pair_kernel(PairConst C, PairData D, double *r0, double *r1
     }
 }
 
+// prep_pair_kernel over many resident pairs in one launch (host/resident_pairs.h): one
+// 256-thread workgroup per item (host/pair_set_plan.h: a pair and `count` <= 256 of its
+// correspondences from `first` on).  The pair's records are read at uniform addresses
+// through const __restrict__ pointers (scalar loads) and held by value before the
+// arithmetic, which is prep_pair_kernel's statement for statement: the derived rows are
+// pinned to its bits.  The rows written are rows 6 .. 11 of the pair (PairData::r0 .. b1,
+// const views of the run's own allocation).  Every access is guarded by the item's count:
+// the tail of a pair never touches the next pair's rows.
+__global__ void __launch_bounds__(kPrepItemMax) prep_pairs_kernel(const PairData *__restrict__ Ds,
+                                                                  const PairConst *__restrict__ Cs,
+                                                                  const PrepItem *__restrict__ items) {
+    const PrepItem it = items[blockIdx.x];
+    if ((int)threadIdx.x >= it.count) return;
+    const PairConst C = Cs[it.pair];
+    const PairData D = Ds[it.pair];
+    const int i = it.first + (int)threadIdx.x;
+    if (i >= C.n) return;
+    double *r0 = const_cast<double *>(D.r0), *r1 = const_cast<double *>(D.r1);
+    double *ra0 = const_cast<double *>(D.a0), *ra1 = const_cast<double *>(D.a1);
+    double *rb0 = const_cast<double *>(D.b0), *rb1 = const_cast<double *>(D.b1);
+    const double xa[3] = {D.x0u[i], D.x0v[i], 1.0}, xb[3] = {D.x1u[i], D.x1v[i], 1.0};
+    double a[3], b[3];
+    matvec3(C.K0i, xa, a);
+    matvec3(C.K1i, xb, b);
+    r0[i] = 1.0 / sqrt(dot3(a, a));
+    r1[i] = 1.0 / sqrt(dot3(b, b));
+    { // the rays as corr_rays forms them
+        Corr p;
+        p.x0u = xa[0];
+        p.x0v = xa[1];
+        p.x1u = xb[0];
+        p.x1v = xb[1];
+        p.r0 = p.r1 = 1.0;
+        corr_rays(C, p);
+        ra0[i] = p.a0;
+        ra1[i] = p.a1;
+        rb0[i] = p.b0;
+        rb1[i] = p.b1;
+    }
+}
+
 // the calibrated ray form's correspondence (eval_corr_cal_ray): the rays from
 // prep_pair_kernel, the unit bearing n1 = b r1 (b_2 = 1); x and n0 are not read
 __device__ inline Corr load_corr_ray(const PairData &D, int i) {
@@ -1190,6 +1231,13 @@ hipError_t launch_prep_pair(hipStream_t s, const PairConst &C, const PairData &D
     if (C.n <= 0) return hipSuccess;
     const bool rays = C.variant == kCal && a0 && a1 && b0 && b1;
     prep_pair_kernel<<<(C.n + 255) / 256, 256, 0, s>>>(C, D, r0, r1, rays ? a0 : nullptr, a1, b0, b1);
+    return hipGetLastError();
+}
+
+hipError_t launch_prep_pairs(hipStream_t s, const PairData *Ds, const PairConst *Cs, const PrepItem *items,
+                             int nitems) {
+    if (nitems <= 0) return hipSuccess;
+    prep_pairs_kernel<<<nitems, kPrepItemMax, 0, s>>>(Ds, Cs, items);
     return hipGetLastError();
 }
 
