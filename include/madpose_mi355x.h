@@ -416,6 +416,92 @@ int mp_select_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, co
 int mp_hypothesize_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
                        const int32_t *sample_types, const int32_t *sample_idx, mp_model *models, int32_t *counts,
                        int64_t sample_chunk);
+/* Fixed-budget RANSAC over a pair set in one call, and its two new parts.  Selection
+ * (num_sel, pair_ids), per-entry indexing and the inlier_idx layout as the calls above; the
+ * three entries give MP_EINVAL, before any device call, on the sets mp_hypothesize_set
+ * refuses.
+ *
+ * mp_draw_set: `budget` minimal samples for every selected pair, drawn on the device, in the
+ * form mp_hypothesize_set takes (8 slots per sample, unread slots 0).  sample_counts[j] is
+ * budget, or 0 for a pair too small for the MD solver; entry j's samples start at the running
+ * sum of the counts before it.  The generator is Philox4x32-10 (multipliers 0xD2511F53,
+ * 0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85), key (seed low, seed high), counter
+ * (s, block, pair, 0): s the sample's index within the pair, pair the pair's index in the set
+ * (not its position in the selection: a subset draws what the whole set draws for its pairs),
+ * block = 0, 1, ...; the sample's words are the blocks' four outputs in order.  For a pair
+ * of n correspondences, k_md = 3 (calibrated) or 4, k_pt = 5 / 6 / 7: word 0 gives the type, 1
+ * (point solver) iff (w0 >> 24) < point_share and n >= k_pt; from word 1 on each word w
+ * proposes (uint64(w) * n) >> 32 and slot a takes the next proposal that differs from the
+ * slots before it; after MP_DRAW_BLOCKS blocks the open slots take the smallest unused
+ * indices in ascending order.  point_share 0 .. 256; -1: the set's solver_type decides (128
+ * hybrid, 256 point solver only, 0 MD solver only).  The code is integer-only and shared by
+ * host and device (mp_debug_draw_host: one sample on the host, no device; out[0] the type or
+ * -1 for n < k_md, out[1 .. 8] the slots, out[9] 1 if the ascending fill was used).
+ * MP_EINVAL also: budget < 0, num_sel x budget > 2^22, point_share outside -1 .. 256, null
+ * outputs.
+ *
+ * mp_candidates_set / mp_candidates_fetch: mp_hypothesize_set's arguments and checks, but
+ * only the models that exist come back, packed as mp_select_set takes them.  The number of
+ * models is not known beforehand, so the result takes two calls: mp_candidates_set runs the
+ * stage, keeps the result in the set and reports num_models; the caller allocates and
+ * mp_candidates_fetch copies out models (num_models), model_offsets (num_sel + 1) and, per
+ * model, cand_sample (its sample's index within the pair) and cand_slot, then drops the
+ * result (a second fetch, or one without a result, is MP_EINVAL; a new mp_candidates_set or
+ * mp_pair_set_destroy drops an unfetched one).  The kept result is read by no other call.
+ * Entry j's models are those of its samples in sample order and slot order, with the bytes
+ * mp_hypothesize_set gives those slots (user units).  On the device the slab's counts are
+ * scanned and the models gathered, so counts, models and tags are all that is copied back.
+ *
+ * mp_ransac_set: draw -> hypothesize -> compact -> select -> refine on the resident pairs.
+ * Either budget >= 0 with sample_offsets / sample_types / sample_idx NULL (samples drawn as
+ * mp_draw_set draws them; they never reach the host), or budget -1 with the three given
+ * (mp_hypothesize_set's form and checks).  rounds 0 .. 64; 0 stops after the selection.
+ * Per selected pair: models[j] (user units; all zero without a winner) and results[j].
+ * The call equals, byte for byte, mp_candidates_set on the samples -> mp_select_set on its
+ * output -> mp_refine_set(rounds) on the winners with pair_ids = the pairs that have one:
+ * best_candidate / score_selected / norm_scale are mp_select_result's best_index / best_score
+ * / norm_scale; best_sample / best_slot / best_type the winner's origin (-1 without one);
+ * score_initial .. num_inliers mp_refine_result's -- for a pair without a winner or with
+ * rounds = 0: lm_status -1, rounds_run 0, score_initial = score_final = score_selected and
+ * the selection's lists.  inlier_idx (nullable): entries past num_inliers[t] are unspecified.
+ * A call leaves nothing a later call can see.  MP_EINVAL also: rounds outside 0 .. 64,
+ * negative sample_chunk / model_chunk, both or neither of budget and samples, and the draw's
+ * refusals. */
+#define MP_DRAW_BLOCKS 16
+#define MP_DRAW_POINT_SHARE_MAX 256
+typedef struct mp_ransac_result {
+    double score_selected, score_initial, score_final, norm_scale;
+    int32_t num_samples, num_candidates;
+    int32_t best_candidate, best_sample, best_slot, best_type;
+    int32_t rounds_run, rounds_accepted, lm_status;
+    int32_t num_inliers[3];
+} mp_ransac_result; /* 80 bytes */
+int mp_draw_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+                int32_t point_share, int32_t *sample_types /* num_sel*budget */,
+                int32_t *sample_idx /* num_sel*budget*8 */, int32_t *sample_counts /* num_sel */);
+int mp_debug_draw_host(int variant, int64_t n, uint64_t seed, int32_t point_share, int32_t pair, int32_t s,
+                       int32_t *out /* 10 */);
+int mp_candidates_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                      const int32_t *sample_types, const int32_t *sample_idx, int64_t sample_chunk,
+                      int64_t *num_models);
+int mp_candidates_fetch(mp_pair_set *set, mp_model *models, int64_t *model_offsets, int32_t *cand_sample,
+                        int32_t *cand_slot);
+int mp_ransac_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+                  int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
+                  const int32_t *sample_idx, int32_t rounds, mp_model *models /* num_sel */,
+                  mp_ransac_result *results /* num_sel */, int32_t *inlier_idx /* nullable */, int64_t sample_chunk,
+                  int64_t model_chunk);
+/* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
+ * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
+ * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the
+ * solve launches, scan + gather, copies back; of the selection: record preparation, upload,
+ * scoring, argmin, winners' sweep; then the bytes the hypothesis stage copied back and the
+ * bytes of the slot array and counts it replaces; last, ms again, the host work on the samples
+ * before the stages (inside the call's time): the check of given samples, or the types of
+ * the drawn ones. */
+#define MP_RANSAC_TIMING_VALUES 18
+int mp_debug_ransac_timing(double *out /* MP_RANSAC_TIMING_VALUES */);
+
 /* Test and measurement hooks.  mp_debug_pair_set_prep: how the pair setups that follow (of
  * sets and of the batch entries; process-wide) derive the calibrated rows -- 0: one launch
  * over all pairs, 1: one launch per pair, the form before; the rows are equal bit for bit.

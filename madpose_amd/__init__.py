@@ -20,6 +20,7 @@ from .api import (  # noqa: F401
     PoseScaleOffsetSharedFocal,
     PoseScaleOffsetTwoFocal,
     RansacOptions,
+    RansacResult,
     RansacStats,
     device_count,
     estimate_batch,

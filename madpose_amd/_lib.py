@@ -26,6 +26,9 @@ SELECT_SLAB_MODELS, SELECT_TILE = 1 << 16, 1
 # slots per sample, model slots per sample by variant (MP_HYPOTHESIZE_*)
 HYPOTHESIZE_SLAB_SAMPLES, HYPOTHESIZE_MAX_SAMPLES, HYPOTHESIZE_SAMPLE_STRIDE = 32768, 1 << 22, 8
 HYPOTHESIZE_SLOTS = (10, 16, 4)
+# mp_draw_set: Philox blocks per sample at most, the largest point_share (MP_DRAW_*);
+# mp_debug_ransac_timing's values
+DRAW_BLOCKS, DRAW_POINT_SHARE_MAX, RANSAC_TIMING_VALUES = 16, 256, 18
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -148,6 +151,25 @@ class mp_select_result(ctypes.Structure):
     ]
 
 
+class mp_ransac_result(ctypes.Structure):
+    _fields_ = [
+        ("score_selected", ctypes.c_double),
+        ("score_initial", ctypes.c_double),
+        ("score_final", ctypes.c_double),
+        ("norm_scale", ctypes.c_double),
+        ("num_samples", ctypes.c_int32),
+        ("num_candidates", ctypes.c_int32),
+        ("best_candidate", ctypes.c_int32),
+        ("best_sample", ctypes.c_int32),
+        ("best_slot", ctypes.c_int32),
+        ("best_type", ctypes.c_int32),
+        ("rounds_run", ctypes.c_int32),
+        ("rounds_accepted", ctypes.c_int32),
+        ("lm_status", ctypes.c_int32),
+        ("num_inliers", ctypes.c_int32 * 3),
+    ]
+
+
 EXPORTS = {
     "mp_select_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
                                        c_double_p, c_double_p, c_double_p, ctypes.POINTER(mp_ransac_options),
@@ -174,6 +196,19 @@ EXPORTS = {
                                      ctypes.c_int64]),
     "mp_hypothesize_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, c_int64_p, c_int32_p, c_int32_p,
                                           ctypes.POINTER(mp_model), c_int32_p, ctypes.c_int64]),
+    "mp_draw_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int32, ctypes.c_uint64,
+                                   ctypes.c_int32, c_int32_p, c_int32_p, c_int32_p]),
+    "mp_debug_draw_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
+                                          ctypes.c_int32, ctypes.c_int32, c_int32_p]),
+    "mp_candidates_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, c_int64_p, c_int32_p, c_int32_p,
+                                         ctypes.c_int64, c_int64_p]),
+    "mp_candidates_fetch": (ctypes.c_int, [ctypes.c_void_p, ctypes.POINTER(mp_model), c_int64_p, c_int32_p,
+                                           c_int32_p]),
+    "mp_ransac_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int32, ctypes.c_uint64,
+                                     ctypes.c_int32, c_int64_p, c_int32_p, c_int32_p, ctypes.c_int32,
+                                     ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
+                                     ctypes.c_int64, ctypes.c_int64]),
+    "mp_debug_ransac_timing": (ctypes.c_int, [c_double_p]),
     "mp_debug_pair_set_prep": (ctypes.c_int, [ctypes.c_int]),
     "mp_debug_pair_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p]),
     "mp_debug_select_tile": (ctypes.c_int, [ctypes.c_int]),

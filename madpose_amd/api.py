@@ -1290,6 +1290,156 @@ class PairSet:
         return _refine_results(self.variant, arr, res, idx, offs)
 
 
+    def _check_draw(self, budget, seed, point_share, ns):
+        if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) or budget < 0:
+            raise ValueError("budget must be a non-negative integer")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
+            raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+        if point_share is not None and (isinstance(point_share, bool) or int(point_share) != point_share
+                                        or not 0 <= point_share <= L.DRAW_POINT_SHARE_MAX):
+            raise ValueError("point_share must be None (the solver type's default) or an integer in 0..256")
+        if ns * int(budget) > L.HYPOTHESIZE_MAX_SAMPLES:
+            raise ValueError(f"at most 2^22 samples per call, got {ns} pairs x {budget}")
+        return int(budget), int(seed), -1 if point_share is None else int(point_share)
+
+    def draw(self, budget, seed, point_share=None, pair_ids=None):
+        """`budget` minimal samples per selected pair, drawn on the device (mp_draw_set): one
+        (types, idx) per pair, the list hypothesize takes.  A pair too small for the MD solver
+        gets none, one too small for the point solver only type 0.  The draw of a pair depends
+        on seed, point_share (of 256: the share of point-solver samples; None: 128 hybrid, 256
+        point solver only, 0 MD solver only, by the set's solver type) and the pair's index in
+        the set, not on the selection."""
+        h = self._live()
+        if self._hyp_error:
+            raise ValueError(self._hyp_error.replace("hypothesize", "draw"))
+        ids, ptr, sizes, _ = self._selection(pair_ids, len(self._sizes) if pair_ids is None else len(pair_ids), "entry")
+        ns = len(sizes)
+        budget, seed, share = self._check_draw(budget, seed, point_share, ns)
+        if ns == 0:
+            return []
+        T = np.zeros(max(ns * budget, 1), dtype=np.int32)
+        I = np.zeros(max(ns * budget, 1) * L.HYPOTHESIZE_SAMPLE_STRIDE, dtype=np.int32)
+        C = np.zeros(ns, dtype=np.int32)
+        L.check(L.lib().mp_draw_set(h, ns, ptr, budget, seed, share, T.ctypes.data_as(L.c_int32_p),
+                                    I.ctypes.data_as(L.c_int32_p), C.ctypes.data_as(L.c_int32_p)))
+        offs = np.concatenate([[0], np.cumsum(C)])
+        I = I.reshape(-1, L.HYPOTHESIZE_SAMPLE_STRIDE)
+        return [(T[offs[j]:offs[j + 1]].copy(), I[offs[j]:offs[j + 1]].copy()) for j in range(ns)]
+
+    def candidates(self, samples, pair_ids=None, sample_chunk=0):
+        """hypothesize on the selected pairs with only the models that exist returned
+        (mp_candidates_set): one (models, sample, slot) per pair -- models float64 of shape
+        (K, 17), select's array candidates: the pair's models in sample order and slot order
+        with hypothesize's bytes; sample and slot int32 of shape (K,), each model's origin."""
+        h = self._live()
+        if self._hyp_error:
+            raise ValueError(self._hyp_error.replace("hypothesize", "candidates"))
+        if isinstance(sample_chunk, bool) or int(sample_chunk) != sample_chunk or sample_chunk < 0:
+            raise ValueError("sample_chunk must be a non-negative integer (0: the default)")
+        ids, ptr, sizes, _ = self._selection(pair_ids, len(samples), "(types, idx)")
+        ns = len(sizes)
+        if ns == 0:
+            return []
+        soffs, T, I = _concat_samples(self.variant, sizes, samples)
+        sample_offsets = np.asarray(soffs, dtype=np.int64)
+        M = ctypes.c_int64(0)
+        L.check(L.lib().mp_candidates_set(h, ns, ptr, sample_offsets.ctypes.data_as(L.c_int64_p),
+                                          T.ctypes.data_as(L.c_int32_p), I.ctypes.data_as(L.c_int32_p),
+                                          int(sample_chunk), ctypes.byref(M)))
+        M = int(M.value)
+        models = np.zeros((max(M, 1), 17))
+        moffs = np.zeros(ns + 1, dtype=np.int64)
+        smp, slot = np.zeros(max(M, 1), dtype=np.int32), np.zeros(max(M, 1), dtype=np.int32)
+        L.check(L.lib().mp_candidates_fetch(h, models.ctypes.data_as(ctypes.POINTER(L.mp_model)),
+                                            moffs.ctypes.data_as(L.c_int64_p), smp.ctypes.data_as(L.c_int32_p),
+                                            slot.ctypes.data_as(L.c_int32_p)))
+        return [(models[moffs[j]:moffs[j + 1]].copy(), smp[moffs[j]:moffs[j + 1]].copy(),
+                 slot[moffs[j]:moffs[j + 1]].copy()) for j in range(ns)]
+
+    def ransac(self, budget=None, seed=0, point_share=None, samples=None, rounds=3, pair_ids=None, sample_chunk=0,
+               model_chunk=0):
+        """Fixed-budget RANSAC on the selected pairs in one call (mp_ransac_set): draw ->
+        hypothesize -> select -> refine on the device-resident pairs.  Exactly one of budget
+        (samples drawn on the device as draw(budget, seed, point_share) draws them) and samples
+        (hypothesize's list).  rounds 0 .. 64; 0 stops after the selection.  Returns one
+        RansacResult per pair, equal byte for byte to candidates(S) -> select ->
+        refine(winners, rounds, pair_ids=the pairs with a winner) on this set."""
+        h = self._live()
+        if self._hyp_error:
+            raise ValueError(self._hyp_error.replace("hypothesize", "ransac"))
+        if (budget is None) == (samples is None):
+            raise ValueError("exactly one of budget and samples must be given")
+        if isinstance(rounds, bool) or int(rounds) != rounds or not 0 <= rounds <= 64:
+            raise ValueError("rounds must be an integer in 0..64")
+        for name, val in (("sample_chunk", sample_chunk), ("model_chunk", model_chunk)):
+            if isinstance(val, bool) or int(val) != val or val < 0:
+                raise ValueError(f"{name} must be a non-negative integer (0: the default)")
+        count = len(samples) if samples is not None else (len(self._sizes) if pair_ids is None else len(pair_ids))
+        ids, ptr, sizes, offs = self._selection(pair_ids, count, "(types, idx)")
+        ns = len(sizes)
+        if samples is None:
+            budget, seed, share = self._check_draw(budget, seed, point_share, ns)
+        if ns == 0:
+            return []
+        if samples is None:
+            so = ty = ix = None
+        else:
+            soffs, T, I = _concat_samples(self.variant, sizes, samples)
+            sample_offsets = np.asarray(soffs, dtype=np.int64)
+            so, ty, ix = (sample_offsets.ctypes.data_as(L.c_int64_p), T.ctypes.data_as(L.c_int32_p),
+                          I.ctypes.data_as(L.c_int32_p))
+            budget, seed, share = -1, 0, -1
+        arr = (L.mp_model * ns)()
+        res = (L.mp_ransac_result * ns)()
+        idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
+        L.check(L.lib().mp_ransac_set(h, ns, ptr, budget, seed, share, so, ty, ix, int(rounds), arr, res,
+                                      idx.ctypes.data_as(L.c_int32_p), int(sample_chunk), int(model_chunk)))
+        out = []
+        for j in range(ns):
+            n, q = sizes[j], res[j]
+            r = RansacResult()
+            r.num_samples, r.num_candidates = int(q.num_samples), int(q.num_candidates)
+            r.index, r.sample, r.slot, r.solver_type = (int(q.best_candidate), int(q.best_sample), int(q.best_slot),
+                                                        int(q.best_type))
+            r.score_selected = float(q.score_selected)
+            r.score_initial, r.score_final = float(q.score_initial), float(q.score_final)
+            r.rounds_run, r.rounds_accepted, r.status = int(q.rounds_run), int(q.rounds_accepted), int(q.lm_status)
+            r.norm_scale = float(q.norm_scale)
+            r.model_row = np.frombuffer(bytes(arr[j]), dtype=np.float64).copy()
+            r.model = _model_from_c(arr[j], self.variant) if r.index >= 0 else None
+            base = 3 * offs[j]
+            r.inlier_indices = [idx[base + t * n: base + t * n + q.num_inliers[t]].copy() for t in range(3)]
+            out.append(r)
+        return out
+
+
+class RansacResult:
+    """One pair's outcome of PairSet.ransac: num_samples, num_candidates; index (the winner
+    among the pair's candidates; -1: none), sample and slot (its origin), solver_type (0 the
+    MD solver, 1 the point solver); score_selected (select's score; DBL_MAX without a winner);
+    score_initial, score_final, rounds_run, rounds_accepted, status (refine's; without a
+    winner or with rounds = 0: status -1, no round, score_final = score_selected); model (a
+    pose object in user units, None without a winner) and model_row (its 17 doubles in mp_model
+    order, zeros without a winner); inlier_indices (three int32 arrays, the returned
+    model's); norm_scale."""
+
+    def __init__(self):
+        self.num_samples = self.num_candidates = 0
+        self.index = self.sample = self.slot = self.solver_type = -1
+        self.score_selected = self.score_initial = self.score_final = float(np.finfo(np.float64).max)
+        self.rounds_run = self.rounds_accepted = 0
+        self.status = -1
+        self.model = None
+        self.model_row = np.zeros(17)
+        self.inlier_indices = [np.zeros(0, dtype=np.int32) for _ in range(3)]
+        self.norm_scale = 1.0
+
+    def __repr__(self):
+        return (f"RansacResult(index={self.index} of {self.num_candidates}, score {self.score_selected:.6g} -> "
+                f"{self.score_final:.6g}, rounds {self.rounds_accepted}/{self.rounds_run}, status={self.status}, "
+                f"inliers={[len(a) for a in self.inlier_indices]})")
+
+
 def score_models(variant, x0, x1, depth0, depth1, cam0, cam1, options, est_config, models, with_errors=False,
                  host_lo=False, fast_bounds=None):
     """Device ScoreModel over explicit models given in problem units (tests / diagnostics).

@@ -13,6 +13,7 @@
 #include "host/pair_set_plan.h"
 #include "host/rng.h"
 #include "host/select_plan.h"
+#include "include/mp_draw.h"
 
 namespace {
 
@@ -345,6 +346,73 @@ int mp_hypothesize_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_id
     return guarded([&]() {
         mp::hypothesize_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, sample_offsets, sample_types,
                             sample_idx, reinterpret_cast<mp::Model *>(models), counts, sample_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_draw_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+                int32_t point_share, int32_t *sample_types, int32_t *sample_idx, int32_t *sample_counts) {
+    return guarded([&]() {
+        mp::draw_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, budget, seed, point_share, sample_types,
+                     sample_idx, sample_counts);
+        return MP_OK;
+    });
+}
+
+int mp_debug_draw_host(int variant, int64_t n, uint64_t seed, int32_t point_share, int32_t pair, int32_t s,
+                       int32_t *out) {
+    return guarded([&]() {
+        mp::draw_host(variant, n, seed, point_share, pair, s, out);
+        return MP_OK;
+    });
+}
+
+int mp_candidates_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                      const int32_t *sample_types, const int32_t *sample_idx, int64_t sample_chunk,
+                      int64_t *num_models) {
+    return guarded([&]() {
+        if (!num_models) throw std::invalid_argument("null num_models");
+        *num_models = 0;
+        *num_models = mp::candidates_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, sample_offsets,
+                                         sample_types, sample_idx, sample_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_candidates_fetch(mp_pair_set *set, mp_model *models, int64_t *model_offsets, int32_t *cand_sample,
+                        int32_t *cand_slot) {
+    return guarded([&]() {
+        mp::candidates_fetch(reinterpret_cast<mp::PairSet *>(set), reinterpret_cast<mp::Model *>(models), model_offsets,
+                             cand_sample, cand_slot);
+        return MP_OK;
+    });
+}
+
+int mp_ransac_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+                  int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
+                  const int32_t *sample_idx, int32_t rounds, mp_model *models, mp_ransac_result *results,
+                  int32_t *inlier_idx, int64_t sample_chunk, int64_t model_chunk) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::RansacResult) == sizeof(mp_ransac_result), "ransac result layout");
+        static_assert(mp::kDrawShareMax == MP_DRAW_POINT_SHARE_MAX && mp::kDrawBlocks == MP_DRAW_BLOCKS,
+                      "draw constants");
+        mp::ransac_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, budget, seed, point_share,
+                       sample_offsets, sample_types, sample_idx, rounds, reinterpret_cast<mp::Model *>(models),
+                       reinterpret_cast<mp::RansacResult *>(results), inlier_idx, sample_chunk, model_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_debug_ransac_timing(double *out_ms) {
+    return guarded([&]() {
+        if (!out_ms) throw std::invalid_argument("null output");
+        const mp::RansacTiming t = mp::ransac_timing_last();
+        const double v[MP_RANSAC_TIMING_VALUES] = {
+            t.total_ms,       t.hypothesize_ms,  t.select_ms,         t.refine_ms,        t.hyp.plan_ms,
+            t.hyp.draw_ms,    t.hyp.upload_ms,   t.hyp.solve_ms,      t.hyp.compact_ms,   t.hyp.download_ms,
+            t.select.prepare_ms, t.select.upload_ms, t.select.score_ms, t.select.argmin_ms, t.select.winners_ms,
+            (double)t.bytes_back, (double)t.bytes_slots, t.samples_ms};
+        for (int i = 0; i < MP_RANSAC_TIMING_VALUES; ++i) out_ms[i] = v[i];
         return MP_OK;
     });
 }

@@ -45,6 +45,7 @@
 #include "../include/mp_score.h"
 #include "../kernels/kernels.h"
 #include "batch_draw.h"
+#include "candidates_plan.h"
 #include "env.h"
 #include "hypothesis_plan.h"
 #include "lo_sweep.h"
@@ -3078,24 +3079,80 @@ struct HypBuffers {
     std::vector<int> h_samples, h_list;
     std::vector<HypItem> h_items;
     HypPlan plan;
-    HypBuffers(int v, int64_t S_all, int64_t sample_chunk)
+    // the compact output mode (HypCompact): the scan's bases, the gathered models, their tags
+    std::unique_ptr<DevArray<int>> d_base, d_tags;
+    std::unique_ptr<DevArray<Model>> d_cmodels;
+    std::vector<int> h_tags;
+    // device-drawn samples (HypDraw): the sampler's items and the types it writes
+    std::unique_ptr<DevArray<DrawItem>> d_ditems;
+    std::unique_ptr<DevArray<int>> d_types;
+    std::vector<DrawItem> h_ditems;
+    HypBuffers(int v, int64_t S_all, int64_t sample_chunk, bool compact = false, bool draw = false)
         : slab_cap(std::min<int64_t>(S_all, hyp_slabs(S_all, sample_chunk)[0].s1)),
           d_samples((size_t)slab_cap * kSampleStride), d_list((size_t)slab_cap), d_counts((size_t)slab_cap),
           d_items((size_t)slab_cap), d_models((size_t)slab_cap * max_models(v)),
           d_cand((size_t)slab_cap * kPtCandStride), d_pen(v == kSF ? (size_t)slab_cap * kPtPenStride : 1),
           d_ncand((size_t)slab_cap), d_valid((size_t)slab_cap * kPtSlotStride),
           d_slots((size_t)slab_cap * kPtSlotStride), W{d_cand.p, d_ncand.p, d_slots.p, d_valid.p, d_pen.p},
-          h_samples((size_t)slab_cap * kSampleStride), h_list((size_t)slab_cap), h_items((size_t)slab_cap) {}
+          h_samples((size_t)slab_cap * kSampleStride), h_list((size_t)slab_cap), h_items((size_t)slab_cap) {
+        if (compact) {
+            d_base.reset(new DevArray<int>((size_t)slab_cap + 1));
+            d_cmodels.reset(new DevArray<Model>((size_t)slab_cap * max_models(v)));
+            d_tags.reset(new DevArray<int>(2 * (size_t)slab_cap * max_models(v)));
+        }
+        if (draw) {
+            // (an item holds at least one sample: a slab has at most slab_cap items)
+            d_ditems.reset(new DevArray<DrawItem>((size_t)slab_cap));
+            d_types.reset(new DevArray<int>((size_t)slab_cap));
+        }
+    }
 };
+
+// The samples of a hypothesize_run drawn on the device instead of given (mp_ransac_set with a
+// budget): the slab's samples are written by launch_draw_samples where the upload would put
+// them, in the same form (the slots a solver does not read are 0), and never reach the
+// host.  sample_types of the run are then the host's draw_type values (word 0 only), which
+// the planning needs, and sample_idx is null.  pair_n: the per-pair sizes on the device.
+struct HypDraw {
+    uint64_t seed;
+    int point_share;
+    const int *d_pair_n;
+};
+// The compact output mode of hypothesize_run (mp_candidates_set, mp_ransac_set): instead of
+// the slot array, only the models that exist come back -- models in (sample, slot) order, in
+// user units, with plan.moff / plan.sample / plan.slot (host/candidates_plan.h).  Per slab
+// the counts (4 bytes per sample), the gathered models and their tags are copied back.
+struct HypCompact {
+    CandPlan plan;
+    std::vector<Model> models;
+    int64_t bytes_back = 0;  // what the slabs copied back
+    int64_t bytes_slots = 0; // what the slot array and the counts would have been
+};
+
+// One slab of device-drawn samples: items of the selection's entries over slab `s`, mapped to
+// the set's pairs, drawn into d_samples / d_types (slab positions).
+void draw_slab(hipStream_t stream, int v, const PairSel sel, const int64_t *soff, const HypSlab &s, const HypDraw &dr,
+               std::vector<DrawItem> &h_items, DrawItem *d_items, int *d_samples, int *d_types) {
+    draw_items(sel.n, soff, s, h_items);
+    if ((int64_t)h_items.size() > s.s1 - s.s0) throw std::logic_error("draw: more items than samples");
+    for (DrawItem &it : h_items) it.pair = sel[it.pair];
+    if (h_items.empty()) return;
+    MP_HIP(hipMemcpyAsync(d_items, h_items.data(), sizeof(DrawItem) * h_items.size(), hipMemcpyHostToDevice, stream));
+    MP_HIP(launch_draw_samples(stream, v, d_items, (int)h_items.size(), dr.d_pair_n, dr.seed, dr.point_share,
+                               d_samples, d_types));
+}
 
 // The sample models of the selected resident pairs (the body of mp_hypothesize_batch and
 // mp_hypothesize_set), S = soff[ns] - soff[0] > 0 samples, checked by check_hyp_samples.
 // soff: ns + 1 offsets into sample_types / sample_idx / counts (models: max_models slots per
 // sample); the run's samples go through the device in slabs (host/hypothesis_plan.h), one
-// launch_hyp_solve each.
+// launch_hyp_solve each.  draw (nullable): the samples are drawn on the device (HypDraw).
+// compact (nullable): the compact output mode (HypCompact; B built for it): `models` is not
+// written, counts still is.  Neither changes a model's bytes.
 void hypothesize_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const int64_t *soff,
                      const int32_t *sample_types, const int32_t *sample_idx, Model *models, int32_t *counts,
-                     int64_t sample_chunk, HypBuffers &B, bool timed, HypTiming &tm) {
+                     int64_t sample_chunk, HypBuffers &B, bool timed, HypTiming &tm, const HypDraw *draw = nullptr,
+                     HypCompact *compact = nullptr) {
     const int ns_sel = sel.n;
     const int v = R.v;
     const int ksz[2] = {v == kCal ? 3 : 4, v == kCal ? 5 : (v == kSF ? 6 : 7)};
@@ -3108,6 +3165,7 @@ void hypothesize_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, co
         ms += 1e3 * secs(t0);
     };
     HypPlan &plan = B.plan;
+    if (compact) compact->plan.begin(ns_sel, soff, maxm);
     for (const HypSlab &s : hyp_slabs(S, sample_chunk)) {
         const int64_t ns = s.s1 - s.s0;
         const int64_t g0 = soff[0] + s.s0; // the slab's first sample in the caller's arrays
@@ -3118,7 +3176,7 @@ void hypothesize_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, co
         if ((int64_t)(nl[0] + nl[1]) != ns || (int64_t)(ni[0] + ni[1]) > ns)
             throw std::logic_error("hypothesize_batch: the slab's lists do not cover its samples");
         // (only the slots a solver reads, range-checked before, reach the device)
-        for (int64_t b = 0; b < ns; ++b) {
+        for (int64_t b = 0; b < ns && !draw; ++b) {
             const int k = ksz[sample_types[g0 + b] != 0 ? 1 : 0];
             const int32_t *q = sample_idx + kSampleStride * (g0 + b);
             int *o = B.h_samples.data() + kSampleStride * b;
@@ -3133,8 +3191,14 @@ void hypothesize_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, co
             for (size_t i = 0; i < ni[0] + ni[1]; ++i) B.h_items[i].pair = sel.ids[B.h_items[i].pair];
         if (timed) tm.plan_ms += 1e3 * secs(t0);
         t0 = Clock::now();
-        MP_HIP(hipMemcpyAsync(B.d_samples.p, B.h_samples.data(), sizeof(int) * kSampleStride * (size_t)ns,
-                              hipMemcpyHostToDevice, stream));
+        if (draw) {
+            draw_slab(stream, v, sel, soff, s, *draw, B.h_ditems, B.d_ditems->p, B.d_samples.p, B.d_types->p);
+            stage_end(t0, tm.draw_ms);
+            t0 = Clock::now();
+        } else {
+            MP_HIP(hipMemcpyAsync(B.d_samples.p, B.h_samples.data(), sizeof(int) * kSampleStride * (size_t)ns,
+                                  hipMemcpyHostToDevice, stream));
+        }
         MP_HIP(hipMemcpyAsync(B.d_list.p, B.h_list.data(), sizeof(int) * (size_t)ns, hipMemcpyHostToDevice, stream));
         MP_HIP(hipMemcpyAsync(B.d_items.p, B.h_items.data(), sizeof(HypItem) * (ni[0] + ni[1]), hipMemcpyHostToDevice,
                               stream));
@@ -3147,6 +3211,47 @@ void hypothesize_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, co
                                 B.d_counts.p));
         stage_end(t0, tm.solve_ms);
         t0 = Clock::now();
+        if (compact) {
+            MP_HIP(launch_hyp_compact(stream, v, B.d_models.p, B.d_counts.p, (int)ns, B.d_base->p, B.d_cmodels->p,
+                                      B.d_tags->p));
+            stage_end(t0, tm.compact_ms);
+            t0 = Clock::now();
+            int total = -1;
+            MP_HIP(hipMemcpyAsync(counts + g0, B.d_counts.p, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipMemcpyAsync(&total, B.d_base->p + ns, sizeof(int), hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipStreamSynchronize(stream));
+            CandPlan &cp = compact->plan;
+            const size_t old_size = compact->models.size();
+            const int64_t nm = cp.add_slab(s, counts + g0); // (refuses a count outside 0 .. maxm)
+            if (nm != total) throw std::runtime_error("hypothesize: the device scan does not match the counts");
+            compact->models.resize(old_size + (size_t)nm);
+            B.h_tags.resize(2 * (size_t)nm);
+            if (nm > 0) {
+                MP_HIP(hipMemcpyAsync(compact->models.data() + old_size, B.d_cmodels->p, sizeof(Model) * (size_t)nm,
+                                      hipMemcpyDeviceToHost, stream));
+                MP_HIP(hipMemcpyAsync(B.h_tags.data(), B.d_tags->p, sizeof(int) * 2 * (size_t)nm, hipMemcpyDeviceToHost,
+                                      stream));
+                MP_HIP(hipStreamSynchronize(stream));
+            }
+            // the device's tags against the plan's; user units as below (one product each)
+            int j = (int)(std::upper_bound(soff, soff + ns_sel + 1, g0) - soff) - 1;
+            for (int64_t m = 0; m < nm; ++m) {
+                const int b = cp.slab_pos[(size_t)m];
+                if (B.h_tags[2 * (size_t)m] != b || B.h_tags[2 * (size_t)m + 1] != cp.slot[old_size + (size_t)m])
+                    throw std::runtime_error("hypothesize: the gathered models are out of order");
+                if (v != kCal) {
+                    while (soff[j + 1] <= g0 + b) ++j;
+                    const double norm = R.norm_scale[sel[j]];
+                    Model &mm = compact->models[old_size + (size_t)m];
+                    mm.focal0 *= norm;
+                    mm.focal1 *= norm;
+                }
+            }
+            compact->bytes_back += (int64_t)sizeof(int) * (ns + 1) + nm * (int64_t)(sizeof(Model) + 2 * sizeof(int));
+            compact->bytes_slots += ns * (int64_t)(sizeof(Model) * maxm + sizeof(int));
+            if (timed) tm.download_ms += 1e3 * secs(t0);
+            continue;
+        }
         Model *out = models + (size_t)g0 * maxm;
         MP_HIP(hipMemcpyAsync(out, B.d_models.p, sizeof(Model) * (size_t)ns * maxm, hipMemcpyDeviceToHost, stream));
         MP_HIP(hipMemcpyAsync(counts + g0, B.d_counts.p, sizeof(int) * (size_t)ns, hipMemcpyDeviceToHost, stream));
@@ -3169,6 +3274,7 @@ void hypothesize_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, co
         }
         if (timed) tm.download_ms += 1e3 * secs(t0);
     }
+    if (compact) compact->plan.finish();
 }
 } // namespace
 
@@ -3276,6 +3382,20 @@ struct PairSet {
     int32_t num_pairs = 0;
     std::vector<char> seen;        // check_selection's scratch
     std::vector<int64_t> out_off;  // the selection's positions in inlier_idx
+    std::unique_ptr<DevArray<int>> d_pair_n; // the pairs' sizes for the sampler, made at the first draw
+    // the candidates of the last candidates_set, until they are fetched (candidates_fetch),
+    // replaced or the set is destroyed; no other call reads them
+    std::unique_ptr<HypCompact> cand;
+    const int *pair_sizes(hipStream_t stream) {
+        if (!d_pair_n) {
+            std::vector<int> hn((size_t)num_pairs);
+            for (int32_t k = 0; k < num_pairs; ++k) hn[(size_t)k] = (int)R->n[(size_t)k];
+            d_pair_n.reset(new DevArray<int>((size_t)num_pairs));
+            MP_HIP(hipMemcpyAsync(d_pair_n->p, hn.data(), sizeof(int) * hn.size(), hipMemcpyHostToDevice, stream));
+            MP_HIP(hipStreamSynchronize(stream)); // (hn dies here)
+        }
+        return d_pair_n->p;
+    }
     // the selection of a call, checked; out_off[j]: the correspondences of the entries before j
     PairSel select(int32_t num_sel, const int32_t *pair_ids) {
         check_selection(num_pairs, num_sel, pair_ids, seen);
@@ -3467,6 +3587,299 @@ void hypothesize_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, con
     if (timed) {
         std::lock_guard<std::mutex> lk2(g_hyp_mu);
         g_hyp_timing = tm;
+    }
+}
+
+namespace {
+std::mutex g_ransac_mu;
+RansacTiming g_ransac_timing;
+
+// the checks mp_hypothesize_set makes on given samples (all before any device call); returns S
+int64_t check_set_samples(const ResidentPairs &R, const PairSel sel, const int64_t *sample_offsets,
+                          const int32_t *sample_types, const int32_t *sample_idx) {
+    if (!sample_offsets) throw std::invalid_argument("null sample_offsets");
+    if (sample_offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+    for (int32_t j = 0; j < sel.n; ++j)
+        if (sample_offsets[j + 1] < sample_offsets[j]) throw std::invalid_argument("offsets must not decrease");
+    const int64_t S = sample_offsets[sel.n] - sample_offsets[0];
+    if (S > kHypSamplesMax) throw std::invalid_argument("more than 2^22 samples");
+    if (S > 0 && (!sample_types || !sample_idx)) throw std::invalid_argument("null sample_types or sample_idx");
+    check_hyp_samples(R.v, sel.n, [&](int32_t j) { return R.n[sel[j]]; }, sample_offsets, sample_types, sample_idx);
+    return S;
+}
+
+void check_draw_args(int32_t num_sel, int32_t budget, int32_t point_share) {
+    if (budget < 0) throw std::invalid_argument("budget must not be negative");
+    if (point_share < -1 || point_share > kDrawShareMax) throw std::invalid_argument("point_share must be in -1..256");
+    if ((int64_t)(num_sel > 0 ? num_sel : 0) * budget > kHypSamplesMax)
+        throw std::invalid_argument("more than 2^22 samples (num_sel x budget)");
+}
+
+// The drawn samples of a selection: budget per entry, none for a pair too small for the MD
+// solver; soff (ns + 1, from 0) and the types from word 0 of each sample's stream (host).
+void draw_plan(const ResidentPairs &R, const PairSel sel, int32_t budget, uint64_t seed, int share,
+               std::vector<int64_t> &soff, std::vector<int32_t> &types) {
+    const int kmd = draw_k_md(R.v), kpt = draw_k_pt(R.v);
+    soff.assign((size_t)sel.n + 1, 0);
+    for (int j = 0; j < sel.n; ++j) soff[(size_t)j + 1] = soff[(size_t)j] + (R.n[sel[j]] >= kmd ? budget : 0);
+    types.resize((size_t)soff[(size_t)sel.n]);
+    for (int j = 0; j < sel.n; ++j) {
+        const int64_t n = R.n[sel[j]];
+        int32_t *t = types.data() + soff[(size_t)j];
+        for (int64_t s = 0; s < soff[(size_t)j + 1] - soff[(size_t)j]; ++s)
+            t[s] = draw_type(n, kpt, seed, share, (uint32_t)sel[j], (uint32_t)s);
+    }
+}
+} // namespace
+
+RansacTiming ransac_timing_last() {
+    std::lock_guard<std::mutex> lk(g_ransac_mu);
+    return g_ransac_timing;
+}
+
+void draw_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+              int32_t point_share, int32_t *sample_types, int32_t *sample_idx, int32_t *sample_counts) {
+    if (!set) throw std::invalid_argument("null pair set");
+    check_draw_args(num_sel, budget, point_share);
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_hyp_supported(set->variant, set->opts, set->cfg);
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        return;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    if (num_sel == 0) return;
+    if (!sample_counts) throw std::invalid_argument("null sample_counts");
+    if (budget > 0 && (!sample_types || !sample_idx)) throw std::invalid_argument("null sample_types or sample_idx");
+    const ResidentPairs &R = *set->R;
+    const int share = point_share < 0 ? draw_default_share(set->cfg.solver_type) : point_share;
+    std::vector<int64_t> soff;
+    std::vector<int32_t> types;
+    draw_plan(R, sel, budget, seed, share, soff, types);
+    for (int j = 0; j < num_sel; ++j) sample_counts[j] = (int32_t)(soff[(size_t)j + 1] - soff[(size_t)j]);
+    const int64_t S = soff[(size_t)num_sel];
+    if (S == 0) return;
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+    const HypDraw dr{seed, share, set->pair_sizes(stream)};
+    const std::vector<HypSlab> slabs = hyp_slabs(S, 0);
+    const size_t cap = (size_t)(slabs[0].s1 - slabs[0].s0);
+    DevArray<DrawItem> d_items(cap);
+    DevArray<int> d_samples(cap * kSampleStride), d_types(cap);
+    std::vector<DrawItem> h_items;
+    for (const HypSlab &s : slabs) {
+        const size_t ns = (size_t)(s.s1 - s.s0);
+        draw_slab(stream, R.v, sel, soff.data(), s, dr, h_items, d_items.p, d_samples.p, d_types.p);
+        MP_HIP(hipMemcpyAsync(sample_idx + kSampleStride * s.s0, d_samples.p, sizeof(int) * kSampleStride * ns,
+                              hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipMemcpyAsync(sample_types + s.s0, d_types.p, sizeof(int) * ns, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+    }
+    // (the planning of mp_ransac_set rests on the host's types being the device's)
+    if (std::memcmp(sample_types, types.data(), sizeof(int32_t) * (size_t)S) != 0)
+        throw std::runtime_error("draw: the device's sample types are not the host's");
+}
+
+void draw_host(int variant, int64_t n, uint64_t seed, int32_t point_share, int32_t pair, int32_t s, int32_t *out) {
+    if (variant < 0 || variant > 2) throw std::invalid_argument("variant must be 0, 1 or 2");
+    if (n < 0 || n > kRefinePairMax) throw std::invalid_argument("n out of range");
+    if (point_share < 0 || point_share > kDrawShareMax) throw std::invalid_argument("point_share must be in 0..256");
+    if (pair < 0 || s < 0 || !out) throw std::invalid_argument("negative pair or sample, or null output");
+    int idx[8];
+    bool fill = false;
+    out[0] = draw_sample(n, draw_k_md(variant), draw_k_pt(variant), seed, point_share, (uint32_t)pair, (uint32_t)s, idx,
+                         &fill);
+    for (int a = 0; a < 8; ++a) out[1 + a] = idx[a];
+    out[9] = fill ? 1 : 0;
+}
+
+int64_t candidates_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                       const int32_t *sample_types, const int32_t *sample_idx, int64_t sample_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_hyp_supported(set->variant, set->opts, set->cfg);
+    set->cand.reset();
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        set->cand.reset(new HypCompact());
+        set->cand->plan.moff.assign(1, 0);
+        return 0;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    std::unique_ptr<HypCompact> co(new HypCompact());
+    static const int64_t kNone[1] = {0};
+    if (num_sel == 0) {
+        co->plan.begin(0, kNone, max_models(set->R->v));
+        co->plan.finish();
+    } else {
+        const ResidentPairs &R = *set->R;
+        const int64_t S = check_set_samples(R, sel, sample_offsets, sample_types, sample_idx);
+        if (S == 0) {
+            co->plan.begin(num_sel, sample_offsets, max_models(R.v));
+            co->plan.finish();
+        } else {
+            const bool timed = g_prof_on.load();
+            HypTiming tm;
+            std::vector<int32_t> counts((size_t)sample_offsets[num_sel]);
+            CtxLease lease(set->device);
+            HypBuffers B(R.v, S, sample_chunk, true, false);
+            hypothesize_run(*set->R, lease.c->stream, sel, sample_offsets, sample_types, sample_idx, nullptr,
+                            counts.data(), sample_chunk, B, timed, tm, nullptr, co.get());
+            if (timed) {
+                std::lock_guard<std::mutex> lk2(g_hyp_mu);
+                g_hyp_timing = tm;
+            }
+        }
+        co->plan.soff = nullptr; // (the caller's array: not read again)
+    }
+    set->cand = std::move(co);
+    return (int64_t)set->cand->models.size();
+}
+
+void candidates_fetch(PairSet *set, Model *models, int64_t *model_offsets, int32_t *cand_sample, int32_t *cand_slot) {
+    if (!set) throw std::invalid_argument("null pair set");
+    std::lock_guard<std::mutex> lk(set->mu);
+    if (!set->cand) throw std::invalid_argument("no candidates to fetch: call mp_candidates_set first");
+    const HypCompact &co = *set->cand;
+    const size_t M = co.models.size();
+    if (!model_offsets) throw std::invalid_argument("null model_offsets");
+    if (M > 0 && (!models || !cand_sample || !cand_slot))
+        throw std::invalid_argument("null models, cand_sample or cand_slot");
+    std::copy(co.plan.moff.begin(), co.plan.moff.end(), model_offsets);
+    if (M > 0) {
+        std::memcpy(models, co.models.data(), sizeof(Model) * M);
+        std::copy(co.plan.sample.begin(), co.plan.sample.end(), cand_sample);
+        std::copy(co.plan.slot.begin(), co.plan.slot.end(), cand_slot);
+    }
+    set->cand.reset();
+}
+
+void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+                int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
+                const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
+                int64_t sample_chunk, int64_t model_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
+    if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
+    if (model_chunk < 0) throw std::invalid_argument("model_chunk must not be negative");
+    const bool given = sample_offsets != nullptr;
+    if (given && budget != -1) throw std::invalid_argument("either samples or a budget: with samples, budget must be -1");
+    if (!given && (sample_types || sample_idx))
+        throw std::invalid_argument("sample_types / sample_idx without sample_offsets");
+    if (!given) check_draw_args(num_sel, budget, point_share);
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_hyp_supported(set->variant, set->opts, set->cfg);
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        return;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    if (num_sel == 0) return;
+    if (!models || !results) throw std::invalid_argument("null models or results");
+    ResidentPairs &R = *set->R;
+    const int v = R.v;
+    std::vector<int64_t> soff_drawn;
+    std::vector<int32_t> types_drawn;
+    const int64_t *soff = sample_offsets;
+    const int32_t *types = sample_types;
+    int share = 0;
+    const bool timed = g_prof_on.load();
+    RansacTiming rt;
+    Clock::time_point t_all = Clock::now();
+    if (given) {
+        check_set_samples(R, sel, sample_offsets, sample_types, sample_idx);
+    } else {
+        share = point_share < 0 ? draw_default_share(set->cfg.solver_type) : point_share;
+        draw_plan(R, sel, budget, seed, share, soff_drawn, types_drawn);
+        soff = soff_drawn.data();
+        types = types_drawn.data();
+    }
+    rt.samples_ms = 1e3 * secs(t_all);
+    const int64_t S = soff[num_sel] - soff[0];
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+
+    // ---- draw -> hypothesize -> compact ----
+    HypCompact co;
+    std::vector<int32_t> counts((size_t)soff[num_sel]);
+    Clock::time_point t0 = Clock::now();
+    if (S > 0) {
+        HypDraw dr{seed, share, nullptr};
+        if (!given) dr.d_pair_n = set->pair_sizes(stream);
+        HypBuffers B(v, S, sample_chunk, true, !given);
+        hypothesize_run(R, stream, sel, soff, types, given ? sample_idx : nullptr, nullptr, counts.data(), sample_chunk,
+                        B, timed, rt.hyp, given ? nullptr : &dr, &co);
+    } else {
+        co.plan.begin(num_sel, soff, max_models(v));
+        co.plan.finish();
+    }
+    rt.hypothesize_ms = 1e3 * secs(t0);
+    rt.bytes_back = co.bytes_back;
+    rt.bytes_slots = co.bytes_slots;
+    const CandPlan &cp = co.plan;
+
+    // ---- select ----
+    t0 = Clock::now();
+    std::vector<SelectResult> sres((size_t)num_sel);
+    const int tile_set = g_select_tile.load();
+    select_run(R, stream, sel, set->out_off.data(), cp.moff.data(), co.models.data(), nullptr, nullptr, sres.data(),
+               inlier_idx, model_chunk, tile_set ? tile_set : kSelectTile, timed, rt.select);
+    rt.select_ms = 1e3 * secs(t0);
+    std::vector<int32_t> win_ids;
+    std::vector<int> win_j;
+    std::vector<int64_t> win_off;
+    std::vector<Model> win_models;
+    for (int j = 0; j < num_sel; ++j) {
+        RansacResult &Q = results[j];
+        std::memset(&Q, 0, sizeof(Q));
+        std::memset(&models[j], 0, sizeof(Model));
+        const SelectResult &B = sres[(size_t)j];
+        Q.num_samples = (int32_t)(soff[j + 1] - soff[j]);
+        Q.num_candidates = (int32_t)(cp.moff[(size_t)j + 1] - cp.moff[(size_t)j]);
+        Q.best_candidate = B.best_index;
+        Q.best_sample = Q.best_slot = Q.best_type = -1;
+        Q.score_selected = Q.score_initial = Q.score_final = B.best_score;
+        Q.norm_scale = B.norm_scale;
+        Q.lm_status = -1;
+        for (int t = 0; t < 3; ++t) Q.num_inliers[t] = B.num_inliers[t];
+        if (B.best_index < 0) continue;
+        cand_origin(cp, j, B.best_index, &Q.best_sample, &Q.best_slot);
+        Q.best_type = types[soff[j] + Q.best_sample];
+        models[j] = co.models[(size_t)(cp.moff[(size_t)j] + B.best_index)];
+        win_j.push_back(j);
+        win_ids.push_back(sel[j]);
+        win_off.push_back(set->out_off[(size_t)j]);
+        win_models.push_back(models[j]);
+    }
+
+    // ---- refine: the pairs with a winner, their lists to their places in the selection ----
+    t0 = Clock::now();
+    if (rounds >= 1 && !win_j.empty()) {
+        const int nw = (int)win_j.size();
+        std::vector<RefineResult> rres((size_t)nw);
+        refine_run(R, stream, PairSel{nw, win_ids.data()}, win_off.data(), set->cfg, rounds, win_models.data(),
+                   rres.data(), inlier_idx);
+        for (int i = 0; i < nw; ++i) {
+            RansacResult &Q = results[win_j[(size_t)i]];
+            const RefineResult &F = rres[(size_t)i];
+            models[win_j[(size_t)i]] = win_models[(size_t)i];
+            Q.score_initial = F.score_initial;
+            Q.score_final = F.score_final;
+            Q.rounds_run = F.rounds_run;
+            Q.rounds_accepted = F.rounds_accepted;
+            Q.lm_status = F.lm_status;
+            for (int t = 0; t < 3; ++t) Q.num_inliers[t] = F.num_inliers[t];
+        }
+    }
+    rt.refine_ms = 1e3 * secs(t0);
+    rt.total_ms = 1e3 * secs(t_all);
+    if (timed) {
+        std::lock_guard<std::mutex> lk2(g_ransac_mu);
+        g_ransac_timing = rt;
     }
 }
 

@@ -178,6 +178,8 @@ struct HypTiming {
     double upload_ms = 0;   // samples, lists and items to the device, the output's zeroing
     double solve_ms = 0;    // the solve launches
     double download_ms = 0; // models and counts back, the focals to user units
+    double draw_ms = 0;     // device-drawn samples only (ransac_set with a budget): the sampler
+    double compact_ms = 0;  // the compact output mode only: the scan and the gather
 };
 HypTiming hypothesize_timing_last();
 
@@ -214,6 +216,52 @@ void select_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const in
 void hypothesize_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
                      const int32_t *sample_types, const int32_t *sample_idx, Model *models, int32_t *counts,
                      int64_t sample_chunk);
+// The fused budget entry and its parts on a pair set (mp_draw_set, mp_candidates_set /
+// mp_candidates_fetch, mp_ransac_set); the selection as in the calls above.
+// draw_set: `budget` samples per selected pair drawn on the device by include/mp_draw.h
+// (counter (s, block, pair of the set, 0), key = seed), in hypothesize_set's form; a pair too
+// small for the MD solver gets none (sample_counts[j] = 0 or budget; the offsets are their
+// running sums).  point_share -1: draw_default_share of the set's solver_type.
+// draw_host: one sample on the host (mp_debug_draw_host; no device): out[0] the type (-1: the
+// pair is too small), out[1 .. 8] the slots, out[9] whether the ascending fill was needed.
+// candidates_set: hypothesize_set's arguments; the models that exist, packed as select_set
+// takes them, are kept in the set until candidates_fetch copies them out (with the
+// num_sel + 1 offsets and, per model, its sample's index within the pair and its slot) and
+// drops them; returns their number.  The bytes are hypothesize_set's for those slots.
+// ransac_set: draw (sample_offsets null, budget >= 0; the samples never reach the host) or
+// the given samples (budget -1) -> hypothesize_run in the compact mode -> select_run ->
+// refine_run on the pairs with a winner (rounds >= 1), under one lock and one lease: the bytes
+// of candidates_set -> select_set -> refine_set(pair_ids = the pairs with a winner).
+struct RansacResult {
+    double score_selected, score_initial, score_final, norm_scale;
+    int32_t num_samples, num_candidates;
+    int32_t best_candidate, best_sample, best_slot, best_type; // -1 without a winner
+    int32_t rounds_run, rounds_accepted;
+    int32_t lm_status; // as RefineResult; -1 without a winner or with rounds = 0
+    int32_t num_inliers[3];
+};
+void draw_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+              int32_t point_share, int32_t *sample_types, int32_t *sample_idx, int32_t *sample_counts);
+void draw_host(int variant, int64_t n, uint64_t seed, int32_t point_share, int32_t pair, int32_t s, int32_t *out);
+int64_t candidates_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
+                       const int32_t *sample_types, const int32_t *sample_idx, int64_t sample_chunk);
+void candidates_fetch(PairSet *set, Model *models, int64_t *model_offsets, int32_t *cand_sample, int32_t *cand_slot);
+void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
+                int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
+                const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
+                int64_t sample_chunk, int64_t model_chunk);
+// Measurement hook (mp_debug_ransac_timing): the last ransac_set made while profiling was
+// enabled; the stages' own splits are waited for, so nothing overlaps.
+struct RansacTiming {
+    double total_ms = 0, hypothesize_ms = 0, select_ms = 0, refine_ms = 0;
+    double samples_ms = 0; // host, before the stages: the check of given samples, or the drawn samples' types
+    HypTiming hyp;
+    SelectTiming select;
+    int64_t bytes_back = 0;  // copied back by the hypothesis stage
+    int64_t bytes_slots = 0; // what the slot array and the counts would have been
+};
+RansacTiming ransac_timing_last();
+
 // Test and measurement hooks (mp_debug_pair_set_prep, mp_debug_pair_set_rows).
 // pair_set_prep_mode: how the following setups (sets and batch entries, process-wide) derive
 // the calibrated rows: 0 one launch_prep_pairs, 1 one launch_prep_pair per pair; returns the

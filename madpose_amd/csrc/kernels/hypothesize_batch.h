@@ -114,7 +114,72 @@ __global__ void __launch_bounds__(64) hyp_compact_kernel(const PairConst *__rest
                               nullptr, counts, maxm);
 }
 
+// ---- the hand-over to select (mp_candidates_set): only the models that exist leave ----
+// After a slab's solve launches, sample b holds counts[b] models at models[b * maxm ..].
+// hyp_scan_counts: base[b] = the models of the samples before b (exclusive scan in sample
+// order), base[ns] their total; one workgroup, thread t owns a contiguous run of samples.  A
+// count outside 0 .. maxm counts as 0 here and in the gather (the host refuses such a slab).
+constexpr int kScanThreads = 1024;
+__global__ void __launch_bounds__(kScanThreads)
+hyp_scan_counts(const int *__restrict__ counts, int ns, int maxm, int *__restrict__ base) {
+    __shared__ int part[kScanThreads];
+    const int t = threadIdx.x;
+    const int per = (ns + kScanThreads - 1) / kScanThreads;
+    const int b0 = min(ns, t * per), b1 = min(ns, b0 + per);
+    auto count_of = [&](int b) {
+        const int c = counts[b];
+        return c < 0 || c > maxm ? 0 : c;
+    };
+    int sum = 0;
+    for (int b = b0; b < b1; ++b) sum += count_of(b);
+    part[t] = sum;
+    __syncthreads();
+    for (int off = 1; off < kScanThreads; off <<= 1) {
+        const int add = t >= off ? part[t - off] : 0;
+        __syncthreads();
+        part[t] += add;
+        __syncthreads();
+    }
+    int run = part[t] - sum;
+    for (int b = b0; b < b1; ++b) {
+        base[b] = run;
+        run += count_of(b);
+    }
+    if (t == kScanThreads - 1) base[ns] = part[t];
+}
+
+// hyp_gather_models: a wave per sample copies its counts[b] models (17 doubles each,
+// contiguous from slot 0) to compact[base[b] ..], a lane per double, and tags each with
+// (slab position, slot).  Reads stay inside the sample's maxm slots (count <= maxm), writes
+// below base[ns] <= ns * maxm, the size of compact and tags.
+constexpr int kGatherWaves = 4;
+__global__ void __launch_bounds__(64 * kGatherWaves)
+hyp_gather_models(const Model *__restrict__ models, const int *__restrict__ counts, const int *__restrict__ base,
+                  int ns, int maxm, Model *__restrict__ compact, int2 *__restrict__ tags) {
+    const int b = blockIdx.x * kGatherWaves + threadIdx.x / 64;
+    const int lane = threadIdx.x % 64;
+    if (b >= ns) return;
+    const int c = counts[b];
+    if (c <= 0 || c > maxm) return;
+    constexpr int kD = (int)(sizeof(Model) / sizeof(double));
+    const double *src = reinterpret_cast<const double *>(models + (size_t)b * maxm);
+    double *dst = reinterpret_cast<double *>(compact + base[b]);
+    for (int i = lane; i < c * kD; i += 64) dst[i] = src[i];
+    if (lane < c) tags[base[b] + lane] = make_int2(b, lane);
+}
+
 } // namespace
+
+hipError_t launch_hyp_compact(hipStream_t s, int variant, const Model *models, const int *counts, int ns, int *base,
+                              Model *compact, int *tags) {
+    if (ns < 0 || ns > kHypSlabSamplesMax) return hipErrorInvalidValue;
+    if (ns == 0) return hipSuccess;
+    const int maxm = max_models(variant);
+    hyp_scan_counts<<<1, kScanThreads, 0, s>>>(counts, ns, maxm, base);
+    hyp_gather_models<<<(ns + kGatherWaves - 1) / kGatherWaves, 64 * kGatherWaves, 0, s>>>(
+        models, counts, base, ns, maxm, compact, reinterpret_cast<int2 *>(tags));
+    return hipGetLastError();
+}
 
 hipError_t launch_hyp_solve(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
                             const HypItem *md_items, int nmd_items, const int *md_list, const HypItem *pt_items,

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../host/pair_set_plan.h"
+#include "../include/mp_draw.h"
 #include "../include/mp_types.h"
 
 namespace mp {
@@ -164,6 +165,19 @@ hipError_t launch_hyp_solve(hipStream_t s, int variant, const PairData *Ds, cons
                             const HypItem *md_items, int nmd_items, const int *md_list, const HypItem *pt_items,
                             int npt_items, const int *pt_list, int npt, const int *samples, const PtWorkspace &W,
                             Model *models, int *counts);
+
+// The hand-over of a slab's models to select (hypothesize_batch.h; mp_candidates_set): after
+// launch_hyp_solve on ns <= 131072 samples, base[b] = the models of the samples before b
+// (ns + 1 ints, base[ns] the total), compact[base[b] + i] = model i of sample b, tags[2 m],
+// tags[2 m + 1] = the slab position and slot of compact model m.  compact and tags are sized
+// for ns * max_models(variant) models.  Two launches: the scan (one workgroup) and the gather.
+hipError_t launch_hyp_compact(hipStream_t s, int variant, const Model *models, const int *counts, int ns, int *base,
+                              Model *compact, int *tags);
+// The device sampler (draw_batch.h; mp_draw_set): item k draws the samples items[k].s0 ..
+// + count - 1 of pair items[k].pair (n = pair_n[pair]) by include/mp_draw.h draw_sample into
+// samples[kSampleStride * (items[k].out + i) ..] and types[items[k].out + i].
+hipError_t launch_draw_samples(hipStream_t s, int variant, const DrawItem *items, int nitems, const int *pair_n,
+                               uint64_t seed, int point_share, int *samples, int *types);
 
 // squared Bougnoux focals of k fundamental matrices (9 doubles each) into out (2 each)
 hipError_t launch_bougnoux(hipStream_t s, const double *F, int64_t k, double *out);

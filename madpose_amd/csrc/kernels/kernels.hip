@@ -1819,3 +1819,5 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 #include "select_batch.h"
 
 #include "hypothesize_batch.h"
+// the device sampler (mp_draw_set, mp_ransac_set)
+#include "draw_batch.h"
