@@ -491,6 +491,43 @@ int mp_ransac_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, in
                   const int32_t *sample_idx, int32_t rounds, mp_model *models /* num_sel */,
                   mp_ransac_result *results /* num_sel */, int32_t *inlier_idx /* nullable */, int64_t sample_chunk,
                   int64_t model_chunk);
+/* mp_ransac_adaptive_set: mp_ransac_set's drawn mode with a per-pair number of samples.  Pair
+ * p's samples are s = 0, 1, 2, ... as mp_draw_set defines them (seed, point_share, the pair's
+ * index in the set).  They go through draw -> hypothesize -> compact -> select in rounds of
+ * `step` per still-active pair; the checkpoints are m_k = min(k step, budget).  A pair's
+ * running best is the strict-< walk over all its candidates so far (the device continues the
+ * walk from the running best's score, so a later round replaces it only with a strictly lower
+ * score).  After round k a pair stops when the estimators' termination rule holds: with c[t]
+ * the three list lengths of the running best, r[t] = c[t] / n (0 for n = 0 or without a
+ * winner), ss[0] = (k_md, k_md, 0), ss[1] = (0, 0, k_pt) and d[s] the number of the pair's
+ * samples 0 .. m_k - 1 of type s, req[s] is: p_all = prod_t pow(r[t], ss[s][t]); p_all <= 0
+ * gives max_num_iterations_per_solver, p_all >= 1 min_num_iterations; p_bad = 1 - p_all >=
+ * 0.99999999999999 gives max_num_iterations_per_solver; otherwise it = ceil(log(1 -
+ * success_probability) / log(p_bad) + 0.5), clamped as a double (not it <
+ * max_num_iterations_per_solver gives that bound); last max(min_num_iterations, value)
+ * (mp_debug_ransac_required: req[0], req[1] on the host, no device).  The pair stops if d[s] >
+ * 0 and d[s] >= req[s] for s = 0 or 1 (stopped[j] = 1), or at m_k = budget (stopped[j] = 0).
+ * A pair too small for the MD solver gets no samples (num_samples 0, stopped 0).
+ * max_num_iterations is not read.  The pairs with a winner are refined once at the end
+ * (rounds 0 .. 64).  results[j].num_samples is the pair's m, and every field of models[j],
+ * results[j] and the pair's lists equals, byte for byte, mp_ransac_set(budget = m, the same
+ * seed, point_share and rounds, pair_ids = that pair).  Nothing on host or device grows with
+ * budget x pairs.  MP_EINVAL also: step < 1, budget < 0 or > 2^20, num_sel x min(step,
+ * budget) > 2^22, rounds outside 0 .. 64, negative sample_chunk / model_chunk, point_share
+ * outside -1 .. 256, and the sets mp_hypothesize_set refuses.
+ * mp_debug_select_argmin (test hook): the argmin launch alone over given scores (pair k's at
+ * model_offsets[k] .. model_offsets[k + 1] - 1, offsets from 0); prior NULL: the launch of
+ * mp_select_set (the walk from DBL_MAX; without a winner index -1, score DBL_MAX); prior given
+ * (one per pair): the walk from prior[k]; no candidate strictly below it: index -1 and score
+ * prior[k]'s bits. */
+int mp_ransac_adaptive_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                           uint64_t seed, int32_t point_share, int32_t rounds, mp_model *models /* num_sel */,
+                           mp_ransac_result *results /* num_sel */, int32_t *inlier_idx /* nullable */,
+                           int32_t *stopped /* num_sel, nullable */, int64_t sample_chunk, int64_t model_chunk);
+int mp_debug_ransac_required(int variant, int64_t n, const int32_t counts[3], const mp_ransac_options *options,
+                             uint32_t req[2]);
+int mp_debug_select_argmin(int32_t num_pairs, const int64_t *model_offsets, const double *scores,
+                           const double *prior /* nullable */, int32_t *index, double *score, int device);
 /* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
  * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
  * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the

@@ -25,6 +25,7 @@ SELECT_SLAB_MODELS, SELECT_TILE = 1 << 16, 1
 # mp_hypothesize_batch: samples per slab when sample_chunk == 0, samples per call, index
 # slots per sample, model slots per sample by variant (MP_HYPOTHESIZE_*)
 HYPOTHESIZE_SLAB_SAMPLES, HYPOTHESIZE_MAX_SAMPLES, HYPOTHESIZE_SAMPLE_STRIDE = 32768, 1 << 22, 8
+RANSAC_ADAPTIVE_MAX_BUDGET = 1 << 20  # mp_ransac_adaptive_set: samples a pair may get at most
 HYPOTHESIZE_SLOTS = (10, 16, 4)
 # mp_draw_set: Philox blocks per sample at most, the largest point_share (MP_DRAW_*);
 # mp_debug_ransac_timing's values
@@ -208,6 +209,14 @@ EXPORTS = {
                                      ctypes.c_int32, c_int64_p, c_int32_p, c_int32_p, ctypes.c_int32,
                                      ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
                                      ctypes.c_int64, ctypes.c_int64]),
+    "mp_ransac_adaptive_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
+                                              c_int32_p, ctypes.c_int64, ctypes.c_int64]),
+    "mp_debug_ransac_required": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_int32_p,
+                                                ctypes.POINTER(mp_ransac_options), ctypes.POINTER(ctypes.c_uint32)]),
+    "mp_debug_select_argmin": (ctypes.c_int, [ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_int32_p,
+                                              c_double_p, ctypes.c_int]),
     "mp_debug_ransac_timing": (ctypes.c_int, [c_double_p]),
     "mp_debug_pair_set_prep": (ctypes.c_int, [ctypes.c_int]),
     "mp_debug_pair_set_rows": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p]),

@@ -1357,16 +1357,30 @@ class PairSet:
                  slot[moffs[j]:moffs[j + 1]].copy()) for j in range(ns)]
 
     def ransac(self, budget=None, seed=0, point_share=None, samples=None, rounds=3, pair_ids=None, sample_chunk=0,
-               model_chunk=0):
+               model_chunk=0, step=None):
         """Fixed-budget RANSAC on the selected pairs in one call (mp_ransac_set): draw ->
         hypothesize -> select -> refine on the device-resident pairs.  Exactly one of budget
         (samples drawn on the device as draw(budget, seed, point_share) draws them) and samples
         (hypothesize's list).  rounds 0 .. 64; 0 stops after the selection.  Returns one
         RansacResult per pair, equal byte for byte to candidates(S) -> select ->
-        refine(winners, rounds, pair_ids=the pairs with a winner) on this set."""
+        refine(winners, rounds, pair_ids=the pairs with a winner) on this set.
+
+        step (None, or an integer >= 1; needs budget, refuses samples): the adaptive mode
+        (mp_ransac_adaptive_set).  The drawn samples go through the device in rounds of `step`
+        per pair, and a pair stops at the first checkpoint min(k step, budget) at which the
+        estimators' termination rule holds on its best candidate so far (the options'
+        success_probability, min_num_iterations and max_num_iterations_per_solver), or at
+        budget.  Each result then equals, byte for byte, ransac(budget=r.num_samples,
+        pair_ids=[that pair]) with the same seed, point_share and rounds; r.stopped tells
+        whether the rule ended the pair."""
         h = self._live()
         if self._hyp_error:
             raise ValueError(self._hyp_error.replace("hypothesize", "ransac"))
+        if step is not None:
+            if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or step < 1:
+                raise ValueError("step must be None (a fixed budget) or an integer >= 1")
+            if samples is not None or budget is None:
+                raise ValueError("step needs a budget and takes no samples: the adaptive mode draws its own")
         if (budget is None) == (samples is None):
             raise ValueError("exactly one of budget and samples must be given")
         if isinstance(rounds, bool) or int(rounds) != rounds or not 0 <= rounds <= 64:
@@ -1377,7 +1391,14 @@ class PairSet:
         count = len(samples) if samples is not None else (len(self._sizes) if pair_ids is None else len(pair_ids))
         ids, ptr, sizes, offs = self._selection(pair_ids, count, "(types, idx)")
         ns = len(sizes)
-        if samples is None:
+        if step is not None:
+            budget, seed, share = self._check_draw(budget, seed, point_share, 0)
+            if budget > L.RANSAC_ADAPTIVE_MAX_BUDGET:
+                raise ValueError("budget must be at most 2^20 in the adaptive mode")
+            # (a round obeys the bound a fixed-budget call obeys)
+            if ns * min(budget, int(step)) > L.HYPOTHESIZE_MAX_SAMPLES:
+                raise ValueError(f"at most 2^22 samples per round, got {ns} pairs x {min(budget, int(step))}")
+        elif samples is None:
             budget, seed, share = self._check_draw(budget, seed, point_share, ns)
         if ns == 0:
             return []
@@ -1392,13 +1413,21 @@ class PairSet:
         arr = (L.mp_model * ns)()
         res = (L.mp_ransac_result * ns)()
         idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
-        L.check(L.lib().mp_ransac_set(h, ns, ptr, budget, seed, share, so, ty, ix, int(rounds), arr, res,
-                                      idx.ctypes.data_as(L.c_int32_p), int(sample_chunk), int(model_chunk)))
+        stopped = np.zeros(ns, dtype=np.int32)
+        if step is not None:
+            L.check(L.lib().mp_ransac_adaptive_set(h, ns, ptr, budget, int(step), seed, share, int(rounds), arr, res,
+                                                   idx.ctypes.data_as(L.c_int32_p),
+                                                   stopped.ctypes.data_as(L.c_int32_p), int(sample_chunk),
+                                                   int(model_chunk)))
+        else:
+            L.check(L.lib().mp_ransac_set(h, ns, ptr, budget, seed, share, so, ty, ix, int(rounds), arr, res,
+                                          idx.ctypes.data_as(L.c_int32_p), int(sample_chunk), int(model_chunk)))
         out = []
         for j in range(ns):
             n, q = sizes[j], res[j]
             r = RansacResult()
             r.num_samples, r.num_candidates = int(q.num_samples), int(q.num_candidates)
+            r.stopped = bool(stopped[j])
             r.index, r.sample, r.slot, r.solver_type = (int(q.best_candidate), int(q.best_sample), int(q.best_slot),
                                                         int(q.best_type))
             r.score_selected = float(q.score_selected)
@@ -1421,10 +1450,12 @@ class RansacResult:
     winner or with rounds = 0: status -1, no round, score_final = score_selected); model (a
     pose object in user units, None without a winner) and model_row (its 17 doubles in mp_model
     order, zeros without a winner); inlier_indices (three int32 arrays, the returned
-    model's); norm_scale."""
+    model's); norm_scale; stopped (the adaptive mode only: the termination rule ended the
+    pair before its budget; False otherwise)."""
 
     def __init__(self):
         self.num_samples = self.num_candidates = 0
+        self.stopped = False
         self.index = self.sample = self.slot = self.solver_type = -1
         self.score_selected = self.score_initial = self.score_final = float(np.finfo(np.float64).max)
         self.rounds_run = self.rounds_accepted = 0

@@ -403,6 +403,36 @@ int mp_ransac_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, in
     });
 }
 
+int mp_ransac_adaptive_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                           uint64_t seed, int32_t point_share, int32_t rounds, mp_model *models,
+                           mp_ransac_result *results, int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk,
+                           int64_t model_chunk) {
+    return guarded([&]() {
+        mp::ransac_adaptive_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, budget, step, seed,
+                                point_share, rounds, reinterpret_cast<mp::Model *>(models),
+                                reinterpret_cast<mp::RansacResult *>(results), inlier_idx, stopped, sample_chunk,
+                                model_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_debug_ransac_required(int variant, int64_t n, const int32_t counts[3], const mp_ransac_options *options,
+                             uint32_t req[2]) {
+    return guarded([&]() {
+        if (!options) throw std::invalid_argument("null options");
+        mp::ransac_required(variant, n, counts, to_opts(options), req);
+        return MP_OK;
+    });
+}
+
+int mp_debug_select_argmin(int32_t num_pairs, const int64_t *model_offsets, const double *scores, const double *prior,
+                           int32_t *index, double *score, int device) {
+    return guarded([&]() {
+        mp::select_argmin_direct(num_pairs, model_offsets, scores, prior, index, score, device);
+        return MP_OK;
+    });
+}
+
 int mp_debug_ransac_timing(double *out_ms) {
     return guarded([&]() {
         if (!out_ms) throw std::invalid_argument("null output");

@@ -27,18 +27,21 @@ namespace mp {
 
 // items[i].pair is the entry's position in the selection (the caller maps it to the set's
 // pair), s0 the first sample's index within the entry, out its slab position
-inline void draw_items(int32_t np, const int64_t *soff, const HypSlab &s, std::vector<DrawItem> &items) {
+// first (nullable): entry k's samples are first[k], first[k] + 1, ... of its pair instead of
+// 0, 1, ... (a later round of mp_ransac_adaptive_set)
+inline void draw_items(int32_t np, const int64_t *soff, const int32_t *first, const HypSlab &s,
+                       std::vector<DrawItem> &items) {
     items.clear();
     if (s.s0 >= s.s1 || np <= 0) return;
     int32_t k = (int32_t)(std::upper_bound(soff, soff + np + 1, s.s0 + soff[0]) - soff) - 1;
     int64_t m = s.s0;
     while (m < s.s1 && k < np) {
-        const int64_t first = soff[k] - soff[0];
+        const int64_t begin = soff[k] - soff[0];
         const int64_t end = std::min(s.s1, soff[k + 1] - soff[0]);
         for (int64_t a = m; a < end; a += kDrawItemSamples) {
             DrawItem it;
             it.pair = k;
-            it.s0 = (int)(a - first);
+            it.s0 = (int)(a - begin) + (first ? first[k] : 0);
             it.count = (int)std::min<int64_t>(kDrawItemSamples, end - a);
             it.out = (int)(a - s.s0);
             items.push_back(it);
@@ -46,6 +49,9 @@ inline void draw_items(int32_t np, const int64_t *soff, const HypSlab &s, std::v
         m = std::max(m, end);
         ++k;
     }
+}
+inline void draw_items(int32_t np, const int64_t *soff, const HypSlab &s, std::vector<DrawItem> &items) {
+    draw_items(np, soff, nullptr, s, items);
 }
 
 struct CandPlan {

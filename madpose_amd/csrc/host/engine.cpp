@@ -50,6 +50,7 @@
 #include "hypothesis_plan.h"
 #include "lo_sweep.h"
 #include "pair_set_plan.h"
+#include "ransac_stop.h"
 #include "refine_plan.h"
 #include "select_plan.h"
 #include "rng.h"
@@ -2767,9 +2768,13 @@ namespace {
 // mp_select_set).  moff: ns + 1 offsets into models / scores / counts (entry j's candidates
 // at moff[j] .. moff[j + 1] - 1); results: entry j; the winner's lists of entry j to
 // inlier_idx + 3 out_off[j] + t n_j (nullable).  List buffer 0 is scratch of the call.
+// prior (nullable; one score per entry): the walk of entry j continues from prior[j], the
+// score of a best it already has (ransac_adaptive_set).  An entry without a candidate
+// strictly below its prior is unchanged: best_index -1, best_score = prior[j], no sweep item,
+// no record, and nothing written to its part of inlier_idx.
 void select_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const int64_t *out_off, const int64_t *moff,
                 const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
-                int64_t model_chunk, int tile, bool timed, SelectTiming &tm) {
+                int64_t model_chunk, int tile, bool timed, SelectTiming &tm, const double *prior = nullptr) {
     const int ns = sel.n;
     if (ns == 0) return;
     const int variant = R.variant, v = R.v;
@@ -2873,7 +2878,14 @@ void select_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
     t0 = Clock::now();
     DevArray<SelectBest> d_best(ns);
     std::vector<SelectBest> best(ns);
-    MP_HIP(launch_select_argmin(stream, d_moff.p, ns, d_scores.p, d_best.p));
+    if (prior) {
+        DevArray<double> d_prior(ns);
+        MP_HIP(hipMemcpyAsync(d_prior.p, prior, sizeof(double) * ns, hipMemcpyHostToDevice, stream));
+        MP_HIP(launch_select_argmin_seeded(stream, d_moff.p, ns, d_scores.p, d_prior.p, d_best.p));
+        MP_HIP(hipStreamSynchronize(stream)); // (d_prior dies here)
+    } else {
+        MP_HIP(launch_select_argmin(stream, d_moff.p, ns, d_scores.p, d_best.p));
+    }
     MP_HIP(hipMemcpyAsync(best.data(), d_best.p, sizeof(SelectBest) * ns, hipMemcpyDeviceToHost, stream));
     if (scores && M > 0)
         MP_HIP(hipMemcpyAsync(scores + moff[0], d_scores.p, sizeof(double) * (size_t)M, hipMemcpyDeviceToHost, stream));
@@ -2890,7 +2902,7 @@ void select_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
     for (int j = 0; j < ns; ++j) {
         SelectResult &Q = results[j];
         std::memset(&Q, 0, sizeof(Q));
-        Q.best_score = DBL_MAX;
+        Q.best_score = prior ? prior[j] : DBL_MAX;
         Q.norm_scale = R.norm_scale[sel[j]];
         Q.best_index = -1;
         if (best[j].index < 0) continue;
@@ -3117,6 +3129,9 @@ struct HypDraw {
     uint64_t seed;
     int point_share;
     const int *d_pair_n;
+    // per entry of the selection, nullable: the entry's samples are first[j], first[j] + 1, ...
+    // of its pair (a later round of ransac_adaptive_set); sample_types are those samples'
+    const int32_t *first = nullptr;
 };
 // The compact output mode of hypothesize_run (mp_candidates_set, mp_ransac_set): instead of
 // the slot array, only the models that exist come back -- models in (sample, slot) order, in
@@ -3133,7 +3148,7 @@ struct HypCompact {
 // the set's pairs, drawn into d_samples / d_types (slab positions).
 void draw_slab(hipStream_t stream, int v, const PairSel sel, const int64_t *soff, const HypSlab &s, const HypDraw &dr,
                std::vector<DrawItem> &h_items, DrawItem *d_items, int *d_samples, int *d_types) {
-    draw_items(sel.n, soff, s, h_items);
+    draw_items(sel.n, soff, dr.first, s, h_items);
     if ((int64_t)h_items.size() > s.s1 - s.s0) throw std::logic_error("draw: more items than samples");
     for (DrawItem &it : h_items) it.pair = sel[it.pair];
     if (h_items.empty()) return;
@@ -3630,6 +3645,56 @@ void draw_plan(const ResidentPairs &R, const PairSel sel, int32_t budget, uint64
             t[s] = draw_type(n, kpt, seed, share, (uint32_t)sel[j], (uint32_t)s);
     }
 }
+// One round of ransac_adaptive_set: entry j takes its pair's samples first[j] ..
+// first[j] + count[j] - 1 (every entry's pair is large enough for the MD solver).
+void draw_plan(const ResidentPairs &R, const PairSel sel, const int32_t *first, const int32_t *count, uint64_t seed,
+               int share, std::vector<int64_t> &soff, std::vector<int32_t> &types) {
+    const int kpt = draw_k_pt(R.v);
+    soff.assign((size_t)sel.n + 1, 0);
+    for (int j = 0; j < sel.n; ++j) soff[(size_t)j + 1] = soff[(size_t)j] + count[j];
+    types.resize((size_t)soff[(size_t)sel.n]);
+    for (int j = 0; j < sel.n; ++j) {
+        const int64_t n = R.n[sel[j]];
+        int32_t *t = types.data() + soff[(size_t)j];
+        for (int32_t s = 0; s < count[j]; ++s)
+            t[s] = draw_type(n, kpt, seed, share, (uint32_t)sel[j], (uint32_t)(first[j] + s));
+    }
+}
+
+// The last stage of ransac_set and ransac_adaptive_set: the entries with a winner
+// (best_candidate >= 0, models[j] the winner) go through one refine_run, their lists to their
+// places in the selection; rounds = 0: nothing.
+void refine_winners(PairSet *set, hipStream_t stream, const PairSel sel, int32_t rounds, Model *models,
+                    RansacResult *results, int32_t *inlier_idx) {
+    if (rounds < 1) return;
+    std::vector<int32_t> win_ids;
+    std::vector<int> win_j;
+    std::vector<int64_t> win_off;
+    std::vector<Model> win_models;
+    for (int j = 0; j < sel.n; ++j) {
+        if (results[j].best_candidate < 0) continue;
+        win_j.push_back(j);
+        win_ids.push_back(sel[j]);
+        win_off.push_back(set->out_off[(size_t)j]);
+        win_models.push_back(models[j]);
+    }
+    if (win_j.empty()) return;
+    const int nw = (int)win_j.size();
+    std::vector<RefineResult> rres((size_t)nw);
+    refine_run(*set->R, stream, PairSel{nw, win_ids.data()}, win_off.data(), set->cfg, rounds, win_models.data(),
+               rres.data(), inlier_idx);
+    for (int i = 0; i < nw; ++i) {
+        RansacResult &Q = results[win_j[(size_t)i]];
+        const RefineResult &F = rres[(size_t)i];
+        models[win_j[(size_t)i]] = win_models[(size_t)i];
+        Q.score_initial = F.score_initial;
+        Q.score_final = F.score_final;
+        Q.rounds_run = F.rounds_run;
+        Q.rounds_accepted = F.rounds_accepted;
+        Q.lm_status = F.lm_status;
+        for (int t = 0; t < 3; ++t) Q.num_inliers[t] = F.num_inliers[t];
+    }
+}
 } // namespace
 
 RansacTiming ransac_timing_last() {
@@ -3829,10 +3894,6 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
     select_run(R, stream, sel, set->out_off.data(), cp.moff.data(), co.models.data(), nullptr, nullptr, sres.data(),
                inlier_idx, model_chunk, tile_set ? tile_set : kSelectTile, timed, rt.select);
     rt.select_ms = 1e3 * secs(t0);
-    std::vector<int32_t> win_ids;
-    std::vector<int> win_j;
-    std::vector<int64_t> win_off;
-    std::vector<Model> win_models;
     for (int j = 0; j < num_sel; ++j) {
         RansacResult &Q = results[j];
         std::memset(&Q, 0, sizeof(Q));
@@ -3850,37 +3911,187 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
         cand_origin(cp, j, B.best_index, &Q.best_sample, &Q.best_slot);
         Q.best_type = types[soff[j] + Q.best_sample];
         models[j] = co.models[(size_t)(cp.moff[(size_t)j] + B.best_index)];
-        win_j.push_back(j);
-        win_ids.push_back(sel[j]);
-        win_off.push_back(set->out_off[(size_t)j]);
-        win_models.push_back(models[j]);
     }
 
     // ---- refine: the pairs with a winner, their lists to their places in the selection ----
     t0 = Clock::now();
-    if (rounds >= 1 && !win_j.empty()) {
-        const int nw = (int)win_j.size();
-        std::vector<RefineResult> rres((size_t)nw);
-        refine_run(R, stream, PairSel{nw, win_ids.data()}, win_off.data(), set->cfg, rounds, win_models.data(),
-                   rres.data(), inlier_idx);
-        for (int i = 0; i < nw; ++i) {
-            RansacResult &Q = results[win_j[(size_t)i]];
-            const RefineResult &F = rres[(size_t)i];
-            models[win_j[(size_t)i]] = win_models[(size_t)i];
-            Q.score_initial = F.score_initial;
-            Q.score_final = F.score_final;
-            Q.rounds_run = F.rounds_run;
-            Q.rounds_accepted = F.rounds_accepted;
-            Q.lm_status = F.lm_status;
-            for (int t = 0; t < 3; ++t) Q.num_inliers[t] = F.num_inliers[t];
-        }
-    }
+    refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
     rt.refine_ms = 1e3 * secs(t0);
     rt.total_ms = 1e3 * secs(t_all);
     if (timed) {
         std::lock_guard<std::mutex> lk2(g_ransac_mu);
         g_ransac_timing = rt;
     }
+}
+
+void ransac_required(int variant, int64_t n, const int32_t *counts, const RansacOptions &opts, uint32_t *req) {
+    if (variant < 0 || variant > 2) throw std::invalid_argument("variant must be 0, 1 or 2");
+    if (n < 0 || n > kRefinePairMax) throw std::invalid_argument("n out of range");
+    if (!counts || !req) throw std::invalid_argument("null counts or output");
+    for (int t = 0; t < 3; ++t)
+        if (counts[t] < 0 || counts[t] > n) throw std::invalid_argument("counts must be in 0..n");
+    const StopOptions so{opts.success_probability, opts.min_num_iterations, opts.max_num_iterations_per_solver};
+    for (int s = 0; s < 2; ++s) req[s] = required_samples(s, draw_k_md(variant), draw_k_pt(variant), n, counts, so);
+}
+
+void select_argmin_direct(int32_t num_pairs, const int64_t *model_offsets, const double *scores, const double *prior,
+                          int32_t *index, double *score, int device) {
+    if (num_pairs < 0) throw std::invalid_argument("negative pair count");
+    if (num_pairs == 0) return;
+    if (!model_offsets || !index || !score) throw std::invalid_argument("null model_offsets, index or score");
+    if (model_offsets[0] != 0) throw std::invalid_argument("model_offsets must start at 0");
+    for (int32_t p = 0; p < num_pairs; ++p)
+        if (model_offsets[p + 1] < model_offsets[p]) throw std::invalid_argument("offsets must not decrease");
+    const int64_t M = model_offsets[num_pairs];
+    if (M > kSelectModelsMax) throw std::invalid_argument("more than 2^28 candidates");
+    if (M > 0 && !scores) throw std::invalid_argument("null scores");
+    CtxLease lease(device);
+    hipStream_t stream = lease.c->stream;
+    DevArray<int64_t> d_moff((size_t)num_pairs + 1);
+    DevArray<double> d_scores((size_t)std::max<int64_t>(M, 1)), d_prior((size_t)num_pairs);
+    DevArray<SelectBest> d_best((size_t)num_pairs);
+    std::vector<SelectBest> best((size_t)num_pairs);
+    MP_HIP(hipMemcpyAsync(d_moff.p, model_offsets, sizeof(int64_t) * ((size_t)num_pairs + 1), hipMemcpyHostToDevice,
+                          stream));
+    if (M > 0) MP_HIP(hipMemcpyAsync(d_scores.p, scores, sizeof(double) * (size_t)M, hipMemcpyHostToDevice, stream));
+    if (prior) {
+        MP_HIP(hipMemcpyAsync(d_prior.p, prior, sizeof(double) * (size_t)num_pairs, hipMemcpyHostToDevice, stream));
+        MP_HIP(launch_select_argmin_seeded(stream, d_moff.p, num_pairs, d_scores.p, d_prior.p, d_best.p));
+    } else {
+        MP_HIP(launch_select_argmin(stream, d_moff.p, num_pairs, d_scores.p, d_best.p));
+    }
+    MP_HIP(hipMemcpyAsync(best.data(), d_best.p, sizeof(SelectBest) * (size_t)num_pairs, hipMemcpyDeviceToHost, stream));
+    MP_HIP(hipStreamSynchronize(stream));
+    for (int32_t p = 0; p < num_pairs; ++p) {
+        if (best[(size_t)p].index >= model_offsets[p + 1] - model_offsets[p])
+            throw std::runtime_error("select_argmin: index out of range");
+        index[p] = best[(size_t)p].index;
+        score[p] = best[(size_t)p].score;
+    }
+}
+
+void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                         uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
+                         int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
+    if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
+    if (model_chunk < 0) throw std::invalid_argument("model_chunk must not be negative");
+    if (step < 1) throw std::invalid_argument("step must be at least 1");
+    if (budget < 0 || budget > kAdaptiveBudgetMax) throw std::invalid_argument("budget must be in 0..2^20");
+    // (a round obeys the bound a fixed-budget call obeys)
+    check_draw_args(num_sel, std::min(step, budget), point_share);
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_hyp_supported(set->variant, set->opts, set->cfg);
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        return;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    if (num_sel == 0) return;
+    if (!models || !results) throw std::invalid_argument("null models or results");
+    ResidentPairs &R = *set->R;
+    const int v = R.v, kmd = draw_k_md(v), kpt = draw_k_pt(v);
+    const int share = point_share < 0 ? draw_default_share(set->cfg.solver_type) : point_share;
+    const StopOptions so{set->opts.success_probability, set->opts.min_num_iterations,
+                         set->opts.max_num_iterations_per_solver};
+    const int tile_set = g_select_tile.load();
+    const int tile = tile_set ? tile_set : kSelectTile;
+
+    // per entry: the running best in results / models; the samples had so far are
+    // results[j].num_samples, the candidates num_candidates, the samples per type drawn[2 j + s]
+    std::vector<int64_t> drawn(2 * (size_t)num_sel, 0);
+    std::vector<int> active; // the entries still sampling, in selection order
+    for (int j = 0; j < num_sel; ++j) {
+        RansacResult &Q = results[j];
+        std::memset(&Q, 0, sizeof(Q));
+        std::memset(&models[j], 0, sizeof(Model));
+        Q.best_candidate = Q.best_sample = Q.best_slot = Q.best_type = -1;
+        Q.score_selected = Q.score_initial = Q.score_final = DBL_MAX;
+        Q.norm_scale = R.norm_scale[sel[j]];
+        Q.lm_status = -1;
+        if (stopped) stopped[j] = 0;
+        if (R.n[sel[j]] >= kmd && budget > 0) active.push_back(j);
+    }
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+    if (!active.empty()) {
+        // (the first round is the largest: its buffers serve every round)
+        HypBuffers B(v, (int64_t)active.size() * std::min(step, budget), sample_chunk, true, true);
+        HypDraw dr{seed, share, set->pair_sizes(stream), nullptr};
+        HypTiming htm;
+        SelectTiming stm;
+        std::vector<int32_t> ids, first, count, types, counts;
+        std::vector<int64_t> out_off, soff;
+        std::vector<double> prior;
+        std::vector<SelectResult> sres;
+        std::vector<int> next;
+        while (!active.empty()) {
+            const int na = (int)active.size();
+            ids.resize((size_t)na);
+            first.resize((size_t)na);
+            count.resize((size_t)na);
+            out_off.resize((size_t)na);
+            prior.resize((size_t)na);
+            sres.resize((size_t)na);
+            for (int a = 0; a < na; ++a) {
+                const int j = active[(size_t)a];
+                ids[(size_t)a] = sel[j];
+                first[(size_t)a] = results[j].num_samples;
+                count[(size_t)a] = round_count(results[j].num_samples, step, budget);
+                out_off[(size_t)a] = set->out_off[(size_t)j];
+                prior[(size_t)a] = results[j].score_selected;
+            }
+            const PairSel asel{na, ids.data()};
+            draw_plan(R, asel, first.data(), count.data(), seed, share, soff, types);
+            const int64_t S = soff[(size_t)na];
+            if (S <= 0 || S > kHypSamplesMax) throw std::logic_error("ransac_adaptive: a round without samples");
+            counts.assign((size_t)S, 0);
+            // ---- draw -> hypothesize -> compact -> select, the walk continued from the prior ----
+            HypCompact co;
+            dr.first = first.data();
+            hypothesize_run(R, stream, asel, soff.data(), types.data(), nullptr, nullptr, counts.data(), sample_chunk, B,
+                            false, htm, &dr, &co);
+            const CandPlan &cp = co.plan;
+            // (with a refinement to come the winners' lists are refine_run's: the rounds copy none)
+            select_run(R, stream, asel, out_off.data(), cp.moff.data(), co.models.data(), nullptr, nullptr, sres.data(),
+                       rounds >= 1 ? nullptr : inlier_idx, model_chunk, tile, false, stm, prior.data());
+            next.clear();
+            for (int a = 0; a < na; ++a) {
+                const int j = active[(size_t)a];
+                RansacResult &Q = results[j];
+                const SelectResult &W = sres[(size_t)a];
+                const int32_t *t = types.data() + soff[(size_t)a];
+                for (int32_t s = 0; s < count[(size_t)a]; ++s) ++drawn[2 * (size_t)j + (t[s] != 0 ? 1 : 0)];
+                if (W.best_index >= 0) { // strictly below the running best: it replaces it
+                    int32_t sample = -1, slot = -1;
+                    cand_origin(cp, a, W.best_index, &sample, &slot);
+                    Q.best_candidate = Q.num_candidates + W.best_index;
+                    Q.best_sample = first[(size_t)a] + sample;
+                    Q.best_slot = slot;
+                    Q.best_type = t[sample];
+                    Q.score_selected = Q.score_initial = Q.score_final = W.best_score;
+                    for (int k = 0; k < 3; ++k) Q.num_inliers[k] = W.num_inliers[k];
+                    models[j] = co.models[(size_t)(cp.moff[(size_t)a] + W.best_index)];
+                }
+                Q.num_samples += count[(size_t)a];
+                Q.num_candidates += (int32_t)(cp.moff[(size_t)a + 1] - cp.moff[(size_t)a]);
+                uint32_t req[2];
+                for (int s = 0; s < 2; ++s)
+                    req[s] = required_samples(s, kmd, kpt, R.n[sel[j]], Q.best_candidate >= 0 ? Q.num_inliers : nullptr,
+                                              so);
+                if (stop_reached(req, &drawn[2 * (size_t)j])) {
+                    if (stopped) stopped[j] = 1;
+                } else if (Q.num_samples < budget) {
+                    next.push_back(j);
+                }
+            }
+            active.swap(next);
+        }
+    }
+    // ---- refine: once, the pairs with a winner ----
+    refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
 }
 
 int solve_md_direct(int variant, const double *x, const double *y, const double *dx, const double *dy, double *sols,

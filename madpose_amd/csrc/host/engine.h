@@ -250,6 +250,26 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
                 int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
                 const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
                 int64_t sample_chunk, int64_t model_chunk);
+// ransac_adaptive_set (mp_ransac_adaptive_set): ransac_set's drawn mode with a per-pair
+// number of samples.  Samples go through draw -> hypothesize_run -> select_run in rounds of
+// `step` per still-active pair (checkpoints m_k = min(k step, budget)); select_run continues
+// each pair's strict-< walk from its running best's score, so the running best is the winner
+// of the walk over all its samples so far.  After a round a pair leaves when the estimators'
+// termination rule (host/ransac_stop.h) holds on its running best's three counts and its
+// samples per type (stopped[j] = 1) or when it has had `budget` samples (stopped[j] = 0).  One
+// refine_run at the end.  Entry j's result equals, byte for byte, ransac_set(budget =
+// results[j].num_samples, pair_ids = that pair).  Nothing grows with budget x pairs: types,
+// counts and candidates are per round.  max_num_iterations is not read.
+void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                         uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
+                         int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk);
+// Test hooks.  ransac_required (mp_debug_ransac_required; no device): req[0], req[1] of the
+// rule for a pair of n correspondences whose best has the list lengths counts[0 .. 2].
+// select_argmin_direct (mp_debug_select_argmin): the argmin launch alone over given scores,
+// seeded with prior (one per pair) or, prior null, the unseeded launch.
+void ransac_required(int variant, int64_t n, const int32_t *counts, const RansacOptions &opts, uint32_t *req);
+void select_argmin_direct(int32_t num_pairs, const int64_t *model_offsets, const double *scores, const double *prior,
+                          int32_t *index, double *score, int device);
 // Measurement hook (mp_debug_ransac_timing): the last ransac_set made while profiling was
 // enabled; the stages' own splits are waited for, so nothing overlaps.
 struct RansacTiming {

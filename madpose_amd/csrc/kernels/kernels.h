@@ -151,6 +151,10 @@ hipError_t launch_select_score(hipStream_t s, int variant, int tile, const PairD
                                double *scores, int *counts);
 // out[k] = GetBestEstimatedModelId's walk over scores[moff[k] .. moff[k + 1]) (np pairs)
 hipError_t launch_select_argmin(hipStream_t s, const int64_t *moff, int np, const double *scores, SelectBest *out);
+// the walk started from prior[k] instead of DBL_MAX: out[k].index = -1 and out[k].score =
+// prior[k] where no candidate is strictly below prior[k] (mp_ransac_adaptive_set)
+hipError_t launch_select_argmin_seeded(hipStream_t s, const int64_t *moff, int np, const double *scores,
+                                       const double *prior, SelectBest *out);
 
 // The estimator's solve stages over explicit samples of the resident pairs
 // (hypothesize_batch.h; mp_hypothesize_batch).  samples: the slab's sample indices

@@ -19,6 +19,7 @@
 //                   over the pair's scores -- each lane over its strided candidates in
 //                   ascending order, then a lexicographic (score, index) reduction in
 //                   which a lane without a winner loses to any lane with one.
+//  select_argmin_seeded  the same walk started from a per-pair prior score.
 #pragma once
 
 namespace mp {
@@ -164,7 +165,59 @@ __global__ void __launch_bounds__(kBlock)
     }
 }
 
+// The walk continued from an earlier one (mp_ransac_adaptive_set): pair k's walk and the
+// reduction start from prior[k], the score its running best already holds, instead of
+// DBL_MAX.  A lane takes a candidate only strictly below the prior, so a lane that holds an
+// index holds a score below the prior (not NaN) and the reduction's order is total as above.
+// No candidate strictly below the prior (an equal one, a NaN one, a NaN prior): index -1 and
+// the prior's own bits as the score -- "unchanged".  A kernel of its own, so the unseeded
+// launch stays the code it was.
+__global__ void __launch_bounds__(kBlock)
+    select_argmin_seeded_kernel(const int64_t *__restrict__ moff, int np, const double *__restrict__ scores,
+                                const double *__restrict__ prior, SelectBest *__restrict__ out) {
+    const int lane = threadIdx.x & 63;
+    const int k = blockIdx.x * kArgminPairs + (threadIdx.x >> 6);
+    if (k >= np) return; // (the whole wave)
+    const int64_t o = moff[k];
+    const int K = (int)(moff[k + 1] - o);
+    const double seed = prior[k];
+    double best = seed;
+    int idx = -1;
+    for (int j = lane; j < K; j += 64) {
+        const double s = scores[o + j];
+        if (s < best) {
+            best = s;
+            idx = j;
+        }
+    }
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ob = __shfl_xor(best, off, 64);
+        const int oi = __shfl_xor(idx, off, 64);
+        const bool take = oi >= 0 && (idx < 0 || ob < best || (ob == best && oi < idx));
+        if (take) {
+            best = ob;
+            idx = oi;
+        }
+    }
+    if (lane == 0) {
+        SelectBest b;
+        b.score = idx >= 0 ? best : seed;
+        b.index = idx;
+        b.pad = 0;
+        out[k] = b;
+    }
+}
+
 } // namespace
+
+hipError_t launch_select_argmin_seeded(hipStream_t s, const int64_t *moff, int np, const double *scores,
+                                       const double *prior, SelectBest *out) {
+    if (np <= 0) return hipSuccess;
+    if (!prior) return hipErrorInvalidValue;
+    select_argmin_seeded_kernel<<<(np + kArgminPairs - 1) / kArgminPairs, kBlock, 0, s>>>(moff, np, scores, prior, out);
+    return hipGetLastError();
+}
 
 hipError_t launch_select_score(hipStream_t s, int variant, int tile, const PairData *Ds, const PairConst *Cs,
                                const SelectItem *items, int nitems, const ScoreRec *recs, int64_t base,
