@@ -528,6 +528,58 @@ int mp_debug_ransac_required(int variant, int64_t n, const int32_t counts[3], co
                              uint32_t req[2]);
 int mp_debug_select_argmin(int32_t num_pairs, const int64_t *model_offsets, const double *scores,
                            const double *prior /* nullable */, int32_t *index, double *score, int device);
+/* mp_refine_relaxed_set: mp_refine_set's arguments and checks, with the estimators' first
+ * local-optimisation fit (LocalOptimization's m_init) as round 0.  The first sweep forms, in
+ * one pass, the tight lists err < thr and the relaxed lists err < thr * threshold_multiplier
+ * (the options of the set; one double product).  Round 0's size test and its least-squares fit
+ * read the relaxed lists; its candidate is accepted as any round's is (LM status 1, score
+ * strictly below score_initial).  Rounds 1 onward read the accepted model's tight lists, as
+ * mp_refine_set's do, and a pair stops at its first round without an accepted model.
+ * score_initial, num_inliers and the returned lists are tight ones throughout.  With
+ * threshold_multiplier 1 the call returns mp_refine_set's bytes.
+ *
+ * mp_ransac_lo_set: mp_ransac_adaptive_set with that fit inside the rounds.  A pair keeps two
+ * tracks.  The minimal track -- score_selected, best_candidate / best_sample / best_slot /
+ * best_type, num_samples, num_candidates -- is mp_ransac_adaptive_set's in every bit: at m
+ * samples it is mp_ransac_set(budget = m, rounds = 0)'s.  The overall best starts empty.  After
+ * a round in which the pair's minimal best was replaced, in this order: (1) the new minimal
+ * model becomes the overall best if its score is strictly below the overall best's (lo_index
+ * -1); (2) the new minimal model gets one local optimisation, mp_refine_relaxed_set with
+ * lo_rounds rounds (lo_runs + 1) -- one call covers all such pairs of the round -- and its
+ * result becomes the overall best if a round of it was accepted and its score_final is
+ * strictly below the overall best's (lo_index = that candidate, lo_accepted + 1).  The
+ * termination rule of mp_ransac_adaptive_set then reads the overall best's three counts;
+ * stopping, continuing and stopped[j] are unchanged.  At the end the overall bests are refined
+ * once (rounds 0 .. 64): models[j], score_initial, score_final, rounds_run, rounds_accepted,
+ * lm_status, num_inliers and the lists describe that refinement; with rounds = 0 they are the
+ * overall best as it stands (score_initial = score_final its score; its lists the selection's
+ * if it is a minimal model, else the ones its local optimisation returned).  The running
+ * bests are kept in user units.  Not done: the num_lo_steps non-minimal samples and the
+ * shrinking-threshold loop of LocalOptimization; lo_starting_iterations is not read; a best
+ * replaced twice within one round gets one local optimisation, at the checkpoint.  Nothing on
+ * host or device grows with budget x pairs.  MP_EINVAL: mp_ransac_adaptive_set's, lo_rounds
+ * outside 1 .. 64, null lo_info. */
+typedef struct mp_ransac_lo_info {
+    int32_t lo_runs, lo_accepted; /* local optimisations run / that became the overall best */
+    int32_t lo_index;             /* the candidate whose LO gave the overall best; -1: a minimal model, or none */
+    int32_t pad;
+} mp_ransac_lo_info; /* 16 bytes */
+int mp_refine_relaxed_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int rounds,
+                          mp_model *models /* in/out, one per selected pair */, mp_refine_result *results,
+                          int32_t *inlier_idx /* nullable */);
+int mp_ransac_lo_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                     uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds,
+                     mp_model *models /* num_sel */, mp_ransac_result *results /* num_sel */,
+                     int32_t *inlier_idx /* nullable */, int32_t *stopped /* num_sel, nullable */,
+                     mp_ransac_lo_info *lo_info /* num_sel */, int64_t sample_chunk, int64_t model_chunk);
+/* Test hook (no device): the two-track bookkeeping walked over num_rounds rounds in each of
+ * which the minimal best was replaced -- its score, counts (3 per round) and candidate index,
+ * and its local optimisation's rounds_accepted, score_final and counts.  score: the overall
+ * best's (DBL_MAX: none); out[0 .. 2] its counts, out[3] lo_index, out[4] lo_runs, out[5]
+ * lo_accepted, out[6] 0 none / 1 a minimal model / 2 a local optimisation's result. */
+int mp_debug_ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts,
+                             const int32_t *candidate, const int32_t *lo_rounds_accepted, const double *lo_score,
+                             const int32_t *lo_counts, double *score, int32_t *out /* 7 */);
 /* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
  * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
  * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the

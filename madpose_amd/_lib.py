@@ -171,6 +171,15 @@ class mp_ransac_result(ctypes.Structure):
     ]
 
 
+class mp_ransac_lo_info(ctypes.Structure):
+    _fields_ = [
+        ("lo_runs", ctypes.c_int32),
+        ("lo_accepted", ctypes.c_int32),
+        ("lo_index", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+    ]
+
+
 EXPORTS = {
     "mp_select_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
                                        c_double_p, c_double_p, c_double_p, ctypes.POINTER(mp_ransac_options),
@@ -213,6 +222,14 @@ EXPORTS = {
                                               ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
                                               ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
                                               c_int32_p, ctypes.c_int64, ctypes.c_int64]),
+    "mp_refine_relaxed_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int,
+                                             ctypes.POINTER(mp_model), ctypes.POINTER(mp_refine_result), c_int32_p]),
+    "mp_ransac_lo_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                        ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
+                                        c_int32_p, ctypes.POINTER(mp_ransac_lo_info), ctypes.c_int64, ctypes.c_int64]),
+    "mp_debug_ransac_lo_track": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_int32_p, c_int32_p, c_int32_p,
+                                                c_double_p, c_int32_p, c_double_p, c_int32_p]),
     "mp_debug_ransac_required": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_int32_p,
                                                 ctypes.POINTER(mp_ransac_options), ctypes.POINTER(ctypes.c_uint32)]),
     "mp_debug_select_argmin": (ctypes.c_int, [ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_int32_p,

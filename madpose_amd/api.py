@@ -1274,9 +1274,16 @@ class PairSet:
                                       idx.ctypes.data_as(L.c_int32_p), int(model_chunk)))
         return _select_results(self.variant, candidates, res, idx, offs, moffs, scores, counts)
 
-    def refine(self, models, rounds=1, pair_ids=None):
-        """refine_batch on the selected pairs: one RefineResult per selected pair."""
+    def refine(self, models, rounds=1, pair_ids=None, relax=False):
+        """refine_batch on the selected pairs: one RefineResult per selected pair.
+
+        relax=True (mp_refine_relaxed_set): round 0 is the estimators' first local-optimisation
+        fit -- its least squares runs over the inliers under the thresholds times the options'
+        threshold_multiplier, formed in the same first sweep as the tight lists; rounds 1 onward
+        and every returned score, count and list are the tight ones."""
         h = self._live()
+        if not isinstance(relax, (bool, np.bool_)):
+            raise ValueError("relax must be True or False")
         if int(rounds) != rounds or not 1 <= rounds <= 64:
             raise ValueError("rounds must be an integer in 1..64")
         ids, ptr, sizes, offs = self._selection(pair_ids, len(models), "model")
@@ -1286,7 +1293,8 @@ class PairSet:
         arr = (L.mp_model * ns)(*[_model_to_c(m, self.variant) for m in models])
         res = (L.mp_refine_result * ns)()
         idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
-        L.check(L.lib().mp_refine_set(h, ns, ptr, int(rounds), arr, res, idx.ctypes.data_as(L.c_int32_p)))
+        entry = L.lib().mp_refine_relaxed_set if relax else L.lib().mp_refine_set
+        L.check(entry(h, ns, ptr, int(rounds), arr, res, idx.ctypes.data_as(L.c_int32_p)))
         return _refine_results(self.variant, arr, res, idx, offs)
 
 
@@ -1357,7 +1365,7 @@ class PairSet:
                  slot[moffs[j]:moffs[j + 1]].copy()) for j in range(ns)]
 
     def ransac(self, budget=None, seed=0, point_share=None, samples=None, rounds=3, pair_ids=None, sample_chunk=0,
-               model_chunk=0, step=None):
+               model_chunk=0, step=None, lo=None):
         """Fixed-budget RANSAC on the selected pairs in one call (mp_ransac_set): draw ->
         hypothesize -> select -> refine on the device-resident pairs.  Exactly one of budget
         (samples drawn on the device as draw(budget, seed, point_share) draws them) and samples
@@ -1372,10 +1380,28 @@ class PairSet:
         success_probability, min_num_iterations and max_num_iterations_per_solver), or at
         budget.  Each result then equals, byte for byte, ransac(budget=r.num_samples,
         pair_ids=[that pair]) with the same seed, point_share and rounds; r.stopped tells
-        whether the rule ended the pair."""
+        whether the rule ended the pair.
+
+        lo (None, or an integer in 1..64; needs step, refuses samples): local optimisation
+        inside the adaptive rounds (mp_ransac_lo_set).  At every checkpoint at which a pair's
+        best minimal model was replaced, that model is first offered to the pair's overall best
+        (strictly lower score wins) and then refined by refine(relax=True, rounds=lo), whose
+        result becomes the overall best if a round was accepted and it scores strictly lower.
+        The termination rule reads the overall best's inlier counts, and the final `rounds`
+        refine the overall best.  index, sample, slot, solver_type, score_selected,
+        num_samples and num_candidates describe the minimal models' walk, as without lo; the
+        model, score_initial, score_final, rounds_*, status and inlier_indices the refined
+        overall best.  lo_runs, lo_accepted: the pair's local optimisations and how many of
+        them became the overall best; lo_index: the candidate whose local optimisation gave
+        the overall best (-1: it is a minimal model)."""
         h = self._live()
         if self._hyp_error:
             raise ValueError(self._hyp_error.replace("hypothesize", "ransac"))
+        if lo is not None:
+            if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not 1 <= lo <= 64:
+                raise ValueError("lo must be None (no local optimisation) or an integer in 1..64")
+            if samples is not None or step is None:
+                raise ValueError("lo needs step and takes no samples: it runs inside the adaptive mode's rounds")
         if step is not None:
             if isinstance(step, bool) or not isinstance(step, (int, np.integer)) or step < 1:
                 raise ValueError("step must be None (a fixed budget) or an integer >= 1")
@@ -1414,7 +1440,14 @@ class PairSet:
         res = (L.mp_ransac_result * ns)()
         idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
         stopped = np.zeros(ns, dtype=np.int32)
-        if step is not None:
+        info = None
+        if lo is not None:
+            info = (L.mp_ransac_lo_info * ns)()
+            L.check(L.lib().mp_ransac_lo_set(h, ns, ptr, budget, int(step), seed, share, int(rounds), int(lo), arr,
+                                             res, idx.ctypes.data_as(L.c_int32_p),
+                                             stopped.ctypes.data_as(L.c_int32_p), info, int(sample_chunk),
+                                             int(model_chunk)))
+        elif step is not None:
             L.check(L.lib().mp_ransac_adaptive_set(h, ns, ptr, budget, int(step), seed, share, int(rounds), arr, res,
                                                    idx.ctypes.data_as(L.c_int32_p),
                                                    stopped.ctypes.data_as(L.c_int32_p), int(sample_chunk),
@@ -1428,6 +1461,9 @@ class PairSet:
             r = RansacResult()
             r.num_samples, r.num_candidates = int(q.num_samples), int(q.num_candidates)
             r.stopped = bool(stopped[j])
+            if info is not None:
+                r.lo_runs, r.lo_accepted, r.lo_index = (int(info[j].lo_runs), int(info[j].lo_accepted),
+                                                        int(info[j].lo_index))
             r.index, r.sample, r.slot, r.solver_type = (int(q.best_candidate), int(q.best_sample), int(q.best_slot),
                                                         int(q.best_type))
             r.score_selected = float(q.score_selected)
@@ -1451,11 +1487,15 @@ class RansacResult:
     pose object in user units, None without a winner) and model_row (its 17 doubles in mp_model
     order, zeros without a winner); inlier_indices (three int32 arrays, the returned
     model's); norm_scale; stopped (the adaptive mode only: the termination rule ended the
-    pair before its budget; False otherwise)."""
+    pair before its budget; False otherwise); lo_runs, lo_accepted, lo_index (ransac(lo=...)
+    only: local optimisations run, those that became the overall best, and the candidate
+    whose local optimisation gave the returned start model; 0, 0 and -1 otherwise)."""
 
     def __init__(self):
         self.num_samples = self.num_candidates = 0
         self.stopped = False
+        self.lo_runs = self.lo_accepted = 0
+        self.lo_index = -1
         self.index = self.sample = self.slot = self.solver_type = -1
         self.score_selected = self.score_initial = self.score_final = float(np.finfo(np.float64).max)
         self.rounds_run = self.rounds_accepted = 0

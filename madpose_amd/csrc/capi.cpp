@@ -416,6 +416,41 @@ int mp_ransac_adaptive_set(mp_pair_set *set, int32_t num_sel, const int32_t *pai
     });
 }
 
+int mp_refine_relaxed_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int rounds, mp_model *models,
+                          mp_refine_result *results, int32_t *inlier_idx) {
+    return guarded([&]() {
+        mp::refine_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, rounds,
+                       reinterpret_cast<mp::Model *>(models), reinterpret_cast<mp::RefineResult *>(results),
+                       inlier_idx, true);
+        return MP_OK;
+    });
+}
+
+int mp_ransac_lo_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                     uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, mp_model *models,
+                     mp_ransac_result *results, int32_t *inlier_idx, int32_t *stopped, mp_ransac_lo_info *lo_info,
+                     int64_t sample_chunk, int64_t model_chunk) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::RansacLoInfo) == sizeof(mp_ransac_lo_info) && sizeof(mp_ransac_lo_info) == 16,
+                      "lo info layout");
+        mp::ransac_lo_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, budget, step, seed, point_share,
+                          rounds, lo_rounds, reinterpret_cast<mp::Model *>(models),
+                          reinterpret_cast<mp::RansacResult *>(results), inlier_idx, stopped,
+                          reinterpret_cast<mp::RansacLoInfo *>(lo_info), sample_chunk, model_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_debug_ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts,
+                             const int32_t *candidate, const int32_t *lo_rounds_accepted, const double *lo_score,
+                             const int32_t *lo_counts, double *score, int32_t *out) {
+    return guarded([&]() {
+        mp::ransac_lo_track(num_rounds, min_score, min_counts, candidate, lo_rounds_accepted, lo_score, lo_counts, score,
+                            out);
+        return MP_OK;
+    });
+}
+
 int mp_debug_ransac_required(int variant, int64_t n, const int32_t counts[3], const mp_ransac_options *options,
                              uint32_t req[2]) {
     return guarded([&]() {

@@ -50,6 +50,7 @@
 #include "hypothesis_plan.h"
 #include "lo_sweep.h"
 #include "pair_set_plan.h"
+#include "ransac_lo_track.h"
 #include "ransac_stop.h"
 #include "refine_plan.h"
 #include "select_plan.h"
@@ -2497,13 +2498,38 @@ void lm_refine_batch_device(const PairInput &in, const RansacOptions &opts, cons
 #include "resident_pairs.h"
 
 namespace {
+// refine_run's device arrays for up to `cap` entries (null there: its own, for the call);
+// ransac_lo_set sizes them once for its selection and passes them to every round's run
+struct RefineBuffers {
+    size_t cap;
+    DevArray<RefineItem> d_items;
+    DevArray<ScoreRec> d_recs;
+    DevArray<RefineSweepOut> d_out;
+    DevArray<LmJob> d_jobs;
+    DevArray<LmPairRef> d_refs;
+    DevArray<Model> d_models;
+    DevArray<int> d_status;
+    std::unique_ptr<DevArray<RelaxedSweepOut>> d_rout; // the relaxed first sweep only
+    RefineBuffers(size_t n, bool relax)
+        : cap(n), d_items(n), d_recs(n), d_out(n), d_jobs(n), d_refs(n), d_models(n), d_status(n) {
+        if (relax) d_rout.reset(new DevArray<RelaxedSweepOut>(n));
+    }
+};
+
 // Refinement of the models of the selected resident pairs (refine_batch's rounds; the body of
 // mp_refine_batch and mp_refine_set).  models / results: entry j of the selection; the
 // accepted models' lists of entry j to inlier_idx + 3 out_off[j] + t n_j (nullable).
 // Per-call state only: each pair's list buffer choice starts at 0, and the lists read are
 // the ones this call wrote.
+// relax (mp_refine_relaxed_set; the local optimisation of ransac_lo_set): the first sweep is
+// launch_refine_sweep_relaxed with the factor `multiplier` (threshold_multiplier), and round 0
+// -- its size test and its LM job -- reads the relaxed counts and lists (the estimators'
+// m_init, LocalOptimization's first act, src/hybrid_ransac.h:383-411); its candidate is swept
+// over the relaxed lists' buffer, which are dead by then.  Everything else, the result's
+// tight counts and lists included, is as without.
 void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const int64_t *out_off,
-                const EstimatorConfig &cfg, int rounds, Model *models, RefineResult *results, int32_t *inlier_idx) {
+                const EstimatorConfig &cfg, int rounds, Model *models, RefineResult *results, int32_t *inlier_idx,
+                bool relax = false, double multiplier = 1.0, RefineBuffers *bufs = nullptr) {
     const int ns = sel.n;
     if (ns == 0) return;
     const int variant = R.variant, v = R.v;
@@ -2528,13 +2554,19 @@ void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
         Q.norm_scale = R.norm_scale[k];
         Q.lm_status = -1;
     }
-    DevArray<RefineItem> d_items(ns);
-    DevArray<ScoreRec> d_recs(ns);
-    DevArray<RefineSweepOut> d_out(ns);
-    DevArray<LmJob> d_jobs(ns);
-    DevArray<LmPairRef> d_refs(ns);
-    DevArray<Model> d_models(ns);
-    DevArray<int> d_status(ns);
+    std::unique_ptr<RefineBuffers> own;
+    if (!bufs) {
+        own.reset(new RefineBuffers(ns, relax));
+        bufs = own.get();
+    }
+    if (bufs->cap < (size_t)ns || (relax && !bufs->d_rout)) throw std::logic_error("refine_run: buffers too small");
+    DevArray<RefineItem> &d_items = bufs->d_items;
+    DevArray<ScoreRec> &d_recs = bufs->d_recs;
+    DevArray<RefineSweepOut> &d_out = bufs->d_out;
+    DevArray<LmJob> &d_jobs = bufs->d_jobs;
+    DevArray<LmPairRef> &d_refs = bufs->d_refs;
+    DevArray<Model> &d_models = bufs->d_models;
+    DevArray<int> &d_status = bufs->d_status;
     std::vector<RefineItem> items;
     std::vector<ScoreRec> recs;
     std::vector<RefineSweepOut> outs;
@@ -2561,11 +2593,39 @@ void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
     // ---- the initial sweep: score and lists of the given models ----
     std::vector<int> running(ns);
     for (int j = 0; j < ns; ++j) running[j] = j;
-    sweep(running, cur, false);
-    for (int j = 0; j < ns; ++j) {
-        RefineResult &Q = results[j];
-        score[j] = Q.score_initial = Q.score_final = outs[j].score;
-        for (int t = 0; t < 3; ++t) Q.num_inliers[t] = outs[j].count[t];
+    std::vector<int> relaxed; // relax: entry j's relaxed counts at 3 j, their lists in its buffer 1
+    if (!relax) {
+        sweep(running, cur, false);
+        for (int j = 0; j < ns; ++j) {
+            RefineResult &Q = results[j];
+            score[j] = Q.score_initial = Q.score_final = outs[j].score;
+            for (int t = 0; t < 3; ++t) Q.num_inliers[t] = outs[j].count[t];
+        }
+    } else {
+        DevArray<RelaxedSweepOut> &d_rout = *bufs->d_rout;
+        std::vector<RelaxedSweepOut> routs(ns);
+        items.resize(ns);
+        recs.resize(ns);
+        for (int j = 0; j < ns; ++j) {
+            items[j].pair = sel[j];
+            items[j].buf = 0;
+            prepare_score_rec(Ch[sel[j]], cur[j], recs[j]);
+        }
+        MP_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(RefineItem) * ns, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_recs.p, recs.data(), sizeof(ScoreRec) * ns, hipMemcpyHostToDevice, stream));
+        MP_HIP(launch_refine_sweep_relaxed(stream, v, R.d_D.p, R.d_C.p, d_items.p, d_recs.p, ns, R.d_list_off.p,
+                                           d_lists, 3 * T, multiplier, d_rout.p));
+        MP_HIP(hipMemcpyAsync(routs.data(), d_rout.p, sizeof(RelaxedSweepOut) * ns, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+        relaxed.resize(3 * (size_t)ns);
+        for (int j = 0; j < ns; ++j) {
+            RefineResult &Q = results[j];
+            score[j] = Q.score_initial = Q.score_final = routs[j].score;
+            for (int t = 0; t < 3; ++t) {
+                Q.num_inliers[t] = routs[j].count[t];
+                relaxed[3 * (size_t)j + t] = routs[j].relaxed[t];
+            }
+        }
     }
     // ---- rounds ----
     std::vector<LmJob> jobs;
@@ -2580,7 +2640,9 @@ void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
             const int k = sel[j];
             RefineResult &Q = results[j];
             ++Q.rounds_run;
-            const int *sz = Q.num_inliers;
+            // (relax: round 0 reads the relaxed lists; every entry is still at buffer 0 then)
+            const bool wide = relax && round == 0;
+            const int *sz = wide ? &relaxed[3 * (size_t)j] : Q.num_inliers;
             // too few data for the solver (the size test of least_squares): the pair stops
             if ((sz[0] < kmd && sz[1] < kmd) || sz[2] < kpt) {
                 Q.lm_status = 3;
@@ -2594,7 +2656,7 @@ void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
             LmPairRef ref;
             ref.pair = k;
             ref.pad = 0;
-            ref.idx_off = refine_list(T, R.off[k], Ch[k].n, buf[j], 0);
+            ref.idx_off = refine_list(T, R.off[k], Ch[k].n, wide ? buf[j] ^ 1 : buf[j], 0);
             refs.push_back(ref);
             which.push_back(j);
         }
@@ -3519,7 +3581,7 @@ void pair_set_rows(const PairSet *set, int32_t pair, double *out) {
 }
 
 void refine_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int rounds, Model *models,
-                RefineResult *results, int32_t *inlier_idx) {
+                RefineResult *results, int32_t *inlier_idx, bool relax) {
     if (!set) throw std::invalid_argument("null pair set");
     if (rounds < 1 || rounds > 64) throw std::invalid_argument("rounds must be in 1..64");
     std::lock_guard<std::mutex> lk(set->mu);
@@ -3532,7 +3594,8 @@ void refine_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int roun
     if (num_sel == 0) return;
     if (!models || !results) throw std::invalid_argument("null models or results");
     CtxLease lease(set->device);
-    refine_run(*set->R, lease.c->stream, sel, set->out_off.data(), set->cfg, rounds, models, results, inlier_idx);
+    refine_run(*set->R, lease.c->stream, sel, set->out_off.data(), set->cfg, rounds, models, results, inlier_idx,
+               relax, set->opts.threshold_multiplier);
 }
 
 void select_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
@@ -4092,6 +4155,210 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     }
     // ---- refine: once, the pairs with a winner ----
     refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
+}
+
+void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
+                   int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
+                   int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
+                   int64_t model_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
+    if (lo_rounds < 1 || lo_rounds > 64) throw std::invalid_argument("lo_rounds must be in 1..64");
+    if (num_sel > 0 && !lo_info) throw std::invalid_argument("null lo_info");
+    if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
+    if (model_chunk < 0) throw std::invalid_argument("model_chunk must not be negative");
+    if (step < 1) throw std::invalid_argument("step must be at least 1");
+    if (budget < 0 || budget > kAdaptiveBudgetMax) throw std::invalid_argument("budget must be in 0..2^20");
+    // (a round obeys the bound a fixed-budget call obeys)
+    check_draw_args(num_sel, std::min(step, budget), point_share);
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_hyp_supported(set->variant, set->opts, set->cfg);
+    if (set->num_pairs == 0) {
+        std::vector<char> seen;
+        check_selection(0, num_sel, pair_ids, seen);
+        return;
+    }
+    const PairSel sel = set->select(num_sel, pair_ids);
+    if (num_sel == 0) return;
+    if (!models || !results) throw std::invalid_argument("null models or results");
+    ResidentPairs &R = *set->R;
+    const int v = R.v, kmd = draw_k_md(v), kpt = draw_k_pt(v);
+    const int share = point_share < 0 ? draw_default_share(set->cfg.solver_type) : point_share;
+    const StopOptions so{set->opts.success_probability, set->opts.min_num_iterations,
+                         set->opts.max_num_iterations_per_solver};
+    const int tile_set = g_select_tile.load();
+    const int tile = tile_set ? tile_set : kSelectTile;
+
+    // per entry, the minimal track: results[j] and minimal[j], as ransac_adaptive_set keeps
+    // them; the overall best: track[j] (host/ransac_lo_track.h) and models[j] (user units)
+    std::vector<Model> minimal((size_t)num_sel);
+    std::vector<LoTrack> track((size_t)num_sel);
+    std::vector<int64_t> drawn(2 * (size_t)num_sel, 0);
+    std::vector<int> active; // the entries still sampling, in selection order
+    for (int j = 0; j < num_sel; ++j) {
+        RansacResult &Q = results[j];
+        std::memset(&Q, 0, sizeof(Q));
+        std::memset(&models[j], 0, sizeof(Model));
+        std::memset(&minimal[(size_t)j], 0, sizeof(Model));
+        Q.best_candidate = Q.best_sample = Q.best_slot = Q.best_type = -1;
+        Q.score_selected = Q.score_initial = Q.score_final = DBL_MAX;
+        Q.norm_scale = R.norm_scale[sel[j]];
+        Q.lm_status = -1;
+        if (stopped) stopped[j] = 0;
+        if (R.n[sel[j]] >= kmd && budget > 0) active.push_back(j);
+    }
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+    if (!active.empty()) {
+        // (the first round is the largest: its buffers serve every round)
+        HypBuffers B(v, (int64_t)active.size() * std::min(step, budget), sample_chunk, true, true);
+        HypDraw dr{seed, share, set->pair_sizes(stream), nullptr};
+        RefineBuffers lo_bufs(active.size(), true);
+        R.lists(2); // (select takes one buffer, the LO both: no regrowth between the rounds)
+        // With rounds = 0 the overall best's lists are the result's.  Both stages write their
+        // lists to `lists` (the selection's layout); an entry's are copied to inlier_idx only
+        // when its model becomes the overall best, so neither track writes over the other's.
+        const bool keep_lists = rounds == 0 && inlier_idx && set->out_off[(size_t)num_sel] > 0;
+        std::vector<int32_t> lists(keep_lists ? 3 * (size_t)set->out_off[(size_t)num_sel] : 0);
+        auto take_lists = [&](int j, const int32_t *counts) {
+            if (!keep_lists) return;
+            const int64_t n = R.n[sel[j]], at = 3 * set->out_off[(size_t)j];
+            for (int t = 0; t < 3; ++t)
+                std::memcpy(inlier_idx + at + t * n, lists.data() + at + t * n, sizeof(int32_t) * (size_t)counts[t]);
+        };
+        HypTiming htm;
+        SelectTiming stm;
+        std::vector<int32_t> ids, first, count, types, counts, lo_ids;
+        std::vector<int64_t> out_off, soff, lo_off;
+        std::vector<double> prior;
+        std::vector<SelectResult> sres;
+        std::vector<int> next, lo_j;
+        std::vector<Model> lo_models;
+        std::vector<RefineResult> lo_res;
+        while (!active.empty()) {
+            const int na = (int)active.size();
+            ids.resize((size_t)na);
+            first.resize((size_t)na);
+            count.resize((size_t)na);
+            out_off.resize((size_t)na);
+            prior.resize((size_t)na);
+            sres.resize((size_t)na);
+            for (int a = 0; a < na; ++a) {
+                const int j = active[(size_t)a];
+                ids[(size_t)a] = sel[j];
+                first[(size_t)a] = results[j].num_samples;
+                count[(size_t)a] = round_count(results[j].num_samples, step, budget);
+                out_off[(size_t)a] = set->out_off[(size_t)j];
+                prior[(size_t)a] = results[j].score_selected; // (the minimal best's: the walk is the adaptive entry's)
+            }
+            const PairSel asel{na, ids.data()};
+            draw_plan(R, asel, first.data(), count.data(), seed, share, soff, types);
+            const int64_t S = soff[(size_t)na];
+            if (S <= 0 || S > kHypSamplesMax) throw std::logic_error("ransac_lo: a round without samples");
+            counts.assign((size_t)S, 0);
+            // ---- draw -> hypothesize -> compact -> select, the walk continued from the prior ----
+            HypCompact co;
+            dr.first = first.data();
+            hypothesize_run(R, stream, asel, soff.data(), types.data(), nullptr, nullptr, counts.data(), sample_chunk, B,
+                            false, htm, &dr, &co);
+            const CandPlan &cp = co.plan;
+            select_run(R, stream, asel, out_off.data(), cp.moff.data(), co.models.data(), nullptr, nullptr, sres.data(),
+                       keep_lists ? lists.data() : nullptr, model_chunk, tile, false, stm, prior.data());
+            // ---- the minimal track, and step 1 for the entries whose minimal best was replaced ----
+            lo_j.clear();
+            lo_ids.clear();
+            lo_off.clear();
+            lo_models.clear();
+            for (int a = 0; a < na; ++a) {
+                const int j = active[(size_t)a];
+                RansacResult &Q = results[j];
+                const SelectResult &W = sres[(size_t)a];
+                const int32_t *t = types.data() + soff[(size_t)a];
+                for (int32_t s = 0; s < count[(size_t)a]; ++s) ++drawn[2 * (size_t)j + (t[s] != 0 ? 1 : 0)];
+                if (W.best_index >= 0) { // strictly below the minimal best: it replaces it
+                    int32_t sample = -1, slot = -1;
+                    cand_origin(cp, a, W.best_index, &sample, &slot);
+                    Q.best_candidate = Q.num_candidates + W.best_index;
+                    Q.best_sample = first[(size_t)a] + sample;
+                    Q.best_slot = slot;
+                    Q.best_type = t[sample];
+                    Q.score_selected = W.best_score;
+                    minimal[(size_t)j] = co.models[(size_t)(cp.moff[(size_t)a] + W.best_index)];
+                    if (lo_take_minimal(track[(size_t)j], W.best_score, W.num_inliers)) {
+                        models[j] = minimal[(size_t)j];
+                        take_lists(j, W.num_inliers);
+                    }
+                    lo_j.push_back(j);
+                    lo_ids.push_back(sel[j]);
+                    lo_off.push_back(set->out_off[(size_t)j]);
+                    lo_models.push_back(minimal[(size_t)j]);
+                }
+                Q.num_samples += count[(size_t)a];
+                Q.num_candidates += (int32_t)(cp.moff[(size_t)a + 1] - cp.moff[(size_t)a]);
+            }
+            // ---- step 2: one relaxed refinement over the new minimal bests ----
+            if (!lo_j.empty()) {
+                const int nl = (int)lo_j.size();
+                lo_res.resize((size_t)nl);
+                refine_run(R, stream, PairSel{nl, lo_ids.data()}, lo_off.data(), set->cfg, lo_rounds, lo_models.data(),
+                           lo_res.data(), keep_lists ? lists.data() : nullptr, true, set->opts.threshold_multiplier,
+                           &lo_bufs);
+                for (int i = 0; i < nl; ++i) {
+                    const int j = lo_j[(size_t)i];
+                    const RefineResult &F = lo_res[(size_t)i];
+                    if (lo_take_refined(track[(size_t)j], results[j].best_candidate, F.rounds_accepted, F.score_final,
+                                        F.num_inliers)) {
+                        models[j] = lo_models[(size_t)i];
+                        take_lists(j, F.num_inliers);
+                    }
+                }
+            }
+            // ---- the rule, on the overall best's counts ----
+            next.clear();
+            for (int a = 0; a < na; ++a) {
+                const int j = active[(size_t)a];
+                const LoTrack &K = track[(size_t)j];
+                uint32_t req[2];
+                for (int s = 0; s < 2; ++s)
+                    req[s] = required_samples(s, kmd, kpt, R.n[sel[j]], K.source != 0 ? K.counts : nullptr, so);
+                if (stop_reached(req, &drawn[2 * (size_t)j])) {
+                    if (stopped) stopped[j] = 1;
+                } else if (results[j].num_samples < budget) {
+                    next.push_back(j);
+                }
+            }
+            active.swap(next);
+        }
+    }
+    for (int j = 0; j < num_sel; ++j) {
+        RansacResult &Q = results[j];
+        const LoTrack &K = track[(size_t)j];
+        if (K.source != 0) Q.score_initial = Q.score_final = K.score;
+        for (int t = 0; t < 3; ++t) Q.num_inliers[t] = K.counts[t];
+        lo_info[j] = RansacLoInfo{K.lo_runs, K.lo_accepted, K.lo_index, 0};
+    }
+    // ---- refine: once, the overall bests ----
+    refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
+}
+
+void ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts, const int32_t *candidate,
+                     const int32_t *lo_rounds_accepted, const double *lo_score, const int32_t *lo_counts,
+                     double *score, int32_t *out) {
+    if (num_rounds < 0) throw std::invalid_argument("negative round count");
+    if (!score || !out) throw std::invalid_argument("null output");
+    if (num_rounds > 0 && (!min_score || !min_counts || !candidate || !lo_rounds_accepted || !lo_score || !lo_counts))
+        throw std::invalid_argument("null input");
+    LoTrack K;
+    for (int32_t r = 0; r < num_rounds; ++r) {
+        lo_take_minimal(K, min_score[r], min_counts + 3 * (size_t)r);
+        lo_take_refined(K, candidate[r], lo_rounds_accepted[r], lo_score[r], lo_counts + 3 * (size_t)r);
+    }
+    *score = K.score;
+    for (int t = 0; t < 3; ++t) out[t] = K.counts[t];
+    out[3] = K.lo_index;
+    out[4] = K.lo_runs;
+    out[5] = K.lo_accepted;
+    out[6] = K.source;
 }
 
 int solve_md_direct(int variant, const double *x, const double *y, const double *dx, const double *dy, double *sols,

@@ -208,8 +208,13 @@ void pair_set_destroy(PairSet *set); // null: nothing
 void pair_set_info(const PairSet *set, int32_t *variant, int32_t *num_pairs, int64_t *correspondences,
                    int64_t *resident_bytes, int32_t *device);
 void pair_set_norm_scales(const PairSet *set, double *out);
+// relax (mp_refine_relaxed_set): the first sweep also forms the lists under the thresholds
+// times the options' threshold_multiplier, and round 0's size test and least-squares fit read
+// those (the estimators' m_init); the candidate of round 0 is accepted as any other (LM status
+// 1, score strictly below score_initial), rounds 1 onward and every returned count and list
+// are the tight ones
 void refine_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int rounds, Model *models,
-                RefineResult *results, int32_t *inlier_idx);
+                RefineResult *results, int32_t *inlier_idx, bool relax = false);
 void select_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
                 const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
                 int64_t model_chunk);
@@ -263,6 +268,39 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
 void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
                          int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk);
+// ransac_lo_set (mp_ransac_lo_set): ransac_adaptive_set with the estimators' local
+// optimisation prefix inside the rounds, two tracks per pair.  The minimal track is
+// ransac_adaptive_set's in every bit (select_run is seeded with the minimal best's score).
+// The overall best is the lowest score among the minimal bests and the models their LOs
+// returned (host/ransac_lo_track.h): after a round's select, every entry whose minimal best
+// was replaced (1) offers it to the overall best (strict <, select's counts) and (2) gets one
+// LO -- a single refine_run(relax, lo_rounds) over all such entries -- whose result becomes
+// the overall best when a round of it was accepted and its score is strictly lower.  The
+// termination rule reads the overall best's counts; stop, continue and `stopped` are as in
+// ransac_adaptive_set.  At the end one refine_run(rounds) on the overall bests.  In a result,
+// score_selected, best_candidate / sample / slot / type describe the minimal track;
+// score_initial, score_final, rounds_run, rounds_accepted, lm_status, num_inliers, the model
+// and the lists the final refinement of the overall best (rounds = 0: the overall best as it
+// stands, its lists select's or the ones its LO returned).  lo_info: one per entry.  The
+// running bests are held in user units, so every LO start and the final refinement go through
+// refine_run's unit change.  Nothing grows with budget x pairs; the LO's device arrays are
+// sized once for the selection.
+struct RansacLoInfo {
+    int32_t lo_runs, lo_accepted; // LOs run; LOs that became the overall best
+    int32_t lo_index;             // the candidate whose LO produced the overall best; -1: a minimal model (or none)
+    int32_t pad;
+};
+void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
+                   int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
+                   int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
+                   int64_t model_chunk);
+// Test hook (mp_debug_ransac_lo_track; no device): host/ransac_lo_track.h walked over
+// num_rounds rounds in each of which the minimal best was replaced (its score and counts,
+// its candidate index, and its LO's rounds_accepted, score_final and counts).  score: the
+// overall best's; out[0 .. 6]: its counts, lo_index, lo_runs, lo_accepted, source.
+void ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts, const int32_t *candidate,
+                     const int32_t *lo_rounds_accepted, const double *lo_score, const int32_t *lo_counts,
+                     double *score, int32_t *out);
 // Test hooks.  ransac_required (mp_debug_ransac_required; no device): req[0], req[1] of the
 // rule for a pair of n correspondences whose best has the list lengths counts[0 .. 2].
 // select_argmin_direct (mp_debug_select_argmin): the argmin launch alone over given scores,

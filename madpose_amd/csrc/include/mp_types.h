@@ -139,6 +139,12 @@ struct RefineSweepOut {
     double score;
     int count[3], pad;
 };
+// refine_sweep_relaxed_kernel's outcome: the score and the tight lengths as above, and the
+// lengths of the three relaxed lists (err < thr * relax) in the item's other list buffer.
+struct RelaxedSweepOut {
+    double score;
+    int count[3], relaxed[3];
+};
 // One workgroup of select_score_kernel (kernels/select_batch.h; planned by
 // host/select_plan.h): `count` consecutive candidates of pair `pair` (of the run), their
 // records at rec .. rec + count - 1 of the slab on the device.

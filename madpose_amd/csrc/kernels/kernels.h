@@ -137,6 +137,14 @@ hipError_t launch_lm_batch(hipStream_t s, const PairData &D, const PairConst &C,
 hipError_t launch_refine_sweep(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
                                const RefineItem *items, const ScoreRec *recs, int nitems, const int64_t *list_off,
                                int *lists, int64_t buf_stride, RefineSweepOut *out);
+// The same sweep with two thresholds per term in one pass: score and tight lists as above,
+// and the relaxed lists err < thr * relax (ascending, the same layout) written to the item's
+// other list buffer, (buf ^ 1) * buf_stride; out[k].relaxed their lengths.  Both buffers
+// must exist.
+hipError_t launch_refine_sweep_relaxed(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                                       const RefineItem *items, const ScoreRec *recs, int nitems,
+                                       const int64_t *list_off, int *lists, int64_t buf_stride, double relax,
+                                       RelaxedSweepOut *out);
 // launch_lm_batch with job j on pair refs[j].pair, its block lists at idx + refs[j].idx_off
 hipError_t launch_lm_pairs(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs, const LmJob *jobs,
                            const LmPairRef *refs, int njobs, const int *idx, Model *out, int *status);
