@@ -168,6 +168,18 @@ int mp_debug_score_terms(int variant, int64_t n, const double *x0, const double 
                          const mp_estimator_config *config, const mp_model *models, int32_t num_models, double *errors,
                          int32_t *flags, double *taus, double *ties, int device);
 
+/* mp_debug_score_margins: the screening margins of explicit models as the score kernel's
+ * records carry them, formed on the host -- test hook, no device.  per_model: 8 per
+ * model (the per-term bounds tau0, tau1, tau2; the gate windows wz0, wz1, wl; the Sampson
+ * denominator floor kg2; the margin of the sum, tie).  per_pair (nullable, 9): the
+ * thresholds (3) and weights (3) of the three terms after the estimators' option
+ * transform, the normalization scale (1 for calibrated pairs), the Sampson loss scale,
+ * and 1 if the calibrated ray form applies (upper-triangular intrinsics), else 0. */
+int mp_debug_score_margins(int variant, int64_t n, const double *x0, const double *x1, const double *d0,
+                           const double *d1, const double *cam0, const double *cam1,
+                           const mp_ransac_options *options, const mp_estimator_config *config, const mp_model *models,
+                           int32_t num_models, double *per_model, double *per_pair);
+
 /* mp_debug_lo_sweep: the same models through the engine's host LO sweep
  * (madpose_amd/csrc/host/lo_sweep.h), the sweep LocalOptimization and
  * UpdateRANSACTerminationCriteria use (src/hybrid_ransac.h:265-349, 383-538): errors

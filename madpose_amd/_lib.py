@@ -291,6 +291,10 @@ EXPORTS = {
                                             ctypes.POINTER(mp_estimator_config), ctypes.POINTER(mp_model),
                                             ctypes.c_int32, c_double_p, c_int32_p, c_double_p, c_double_p,
                                             ctypes.c_int]),
+    "mp_debug_score_margins": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p, c_double_p,
+                                              c_double_p, c_double_p, c_double_p, ctypes.POINTER(mp_ransac_options),
+                                              ctypes.POINTER(mp_estimator_config), ctypes.POINTER(mp_model),
+                                              ctypes.c_int32, c_double_p, c_double_p]),
     "mp_debug_lo_sweep": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p, c_double_p, c_double_p,
                                          c_double_p, c_double_p, ctypes.POINTER(mp_ransac_options),
                                          ctypes.POINTER(mp_estimator_config), ctypes.POINTER(mp_model), ctypes.c_int32,

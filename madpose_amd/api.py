@@ -1610,6 +1610,34 @@ def debug_score_terms(variant, x0, x1, depth0, depth1, cam0, cam1, options, est_
             ties[:nm])
 
 
+def debug_score_margins(variant, x0, x1, depth0, depth1, cam0, cam1, options, est_config, models):
+    """The screening margins of explicit models, formed on the host (test hook,
+    mp_debug_score_margins; no device).  Returns (per model: dict of taus [nm x 3], wz0,
+    wz1, wl, kg2, tie [nm each]; per pair: dict of thr [3], w [3], norm_scale, loss_scale,
+    kstd)."""
+    x0 = _pts(x0, "x0")
+    x1 = _pts(x1, "x1")
+    n = x0.shape[0]
+    d0 = _vec(depth0, n, "depth0")
+    d1 = _vec(depth1, n, "depth1")
+    c0 = np.ascontiguousarray(np.asarray(cam0, dtype=np.float64).reshape(-1))
+    c1 = np.ascontiguousarray(np.asarray(cam1, dtype=np.float64).reshape(-1))
+    nm = len(models)
+    arr = (L.mp_model * max(nm, 1))(*[_model_to_c(m, variant) for m in models])
+    pm = np.zeros((max(nm, 1), 8))
+    pp = np.zeros(9)
+    o = options._to_c()
+    c = (est_config or EstimatorConfig())._to_c()
+    L.check(L.lib().mp_debug_score_margins(variant, n, _dp(x0), _dp(x1), _dp(d0), _dp(d1), _dp(c0), _dp(c1),
+                                           ctypes.byref(o), ctypes.byref(c), arr, nm, _dp(pm), _dp(pp)))
+    pm = pm[:nm]
+    per_model = {"taus": pm[:, 0:3].copy(), "wz0": pm[:, 3].copy(), "wz1": pm[:, 4].copy(), "wl": pm[:, 5].copy(),
+                 "kg2": pm[:, 6].copy(), "tie": pm[:, 7].copy()}
+    per_pair = {"thr": pp[0:3].copy(), "w": pp[3:6].copy(), "norm_scale": float(pp[6]), "loss_scale": float(pp[7]),
+                "kstd": int(pp[8])}
+    return per_model, per_pair
+
+
 def device_count():
     return int(L.lib().mp_device_count())
 

@@ -689,6 +689,21 @@ int mp_debug_score_terms(int variant, int64_t n, const double *x0, const double 
     });
 }
 
+int mp_debug_score_margins(int variant, int64_t n, const double *x0, const double *x1, const double *d0,
+                           const double *d1, const double *cam0, const double *cam1,
+                           const mp_ransac_options *options, const mp_estimator_config *config, const mp_model *models,
+                           int32_t num_models, double *per_model, double *per_pair) {
+    return guarded([&]() {
+        if (!options || !models || !per_model || num_models < 0) throw std::invalid_argument("bad arguments");
+        const double md[2] = {0.0, 0.0};
+        mp::PairInput in = make_input(variant, n, x0, x1, d0, d1, md, cam0, cam1);
+        std::vector<mp::Model> ms(num_models);
+        std::memcpy(ms.data(), models, sizeof(mp_model) * num_models);
+        mp::debug_score_margins(in, to_opts(options), to_cfg(config), ms.data(), num_models, per_model, per_pair);
+        return MP_OK;
+    });
+}
+
 int mp_debug_lo_sweep(int variant, int64_t n, const double *x0, const double *x1, const double *d0, const double *d1,
                       const double *cam0, const double *cam1, const mp_ransac_options *options,
                       const mp_estimator_config *config, const mp_model *models, int32_t num_models, double *scores,

@@ -2328,6 +2328,33 @@ void debug_score_terms(const PairInput &in, const RansacOptions &opts, const Est
     MP_HIP(hipStreamSynchronize(X.stream));
 }
 
+// the margins score_batch would use for explicit models, formed on the host as for the
+// device records (mp_debug_score_margins; test hook, no device)
+void debug_score_margins(const PairInput &in, const RansacOptions &opts, const EstimatorConfig &cfg,
+                         const Model *models, int nm, double *per_model, double *per_pair) {
+    validate(in, opts);
+    Problem P = make_problem(in, opts, cfg);
+    for (int m = 0; m < nm; ++m) {
+        ScoreRec r;
+        double *o = per_model + 8 * (size_t)m;
+        prepare_score_rec(P.C, models[m], r, o);
+        o[3] = r.wz0;
+        o[4] = r.wz1;
+        o[5] = r.wl;
+        o[6] = r.kg2;
+        o[7] = r.tie;
+    }
+    if (per_pair) {
+        for (int t = 0; t < 3; ++t) {
+            per_pair[t] = P.C.thr[t];
+            per_pair[3 + t] = P.C.w[t];
+        }
+        per_pair[6] = P.norm_scale;
+        per_pair[7] = P.C.loss_scale;
+        per_pair[8] = P.C.kstd;
+    }
+}
+
 void lo_sweep_models(const PairInput &in, const RansacOptions &opts, const EstimatorConfig &cfg, const Model *models,
                      int nm, double *scores, double *errors, double *fast_bounds) {
     validate(in, opts);

@@ -71,6 +71,12 @@ void lo_sweep_models(const PairInput &in, const RansacOptions &opts, const Estim
 void debug_score_terms(const PairInput &in, const RansacOptions &opts, const EstimatorConfig &cfg, const Model *models,
                        int nm, double *errors, int *flags, double *taus, double *ties, int device);
 
+// score_margins of explicit models on the host, no device (mp_debug_score_margins, test
+// hook): per model taus[3], wz0, wz1, wl, kg2, tie; per pair thr[3], w[3], the
+// normalization scale, the Sampson loss scale, kstd
+void debug_score_margins(const PairInput &in, const RansacOptions &opts, const EstimatorConfig &cfg,
+                         const Model *models, int nm, double *per_model /* 8 nm */, double *per_pair /* 9 */);
+
 // score_batch over explicit models (mp_debug_score_batch; test hook).  models: nb x
 // max_models(variant) (problem units), counts[b] of them used per iteration.  flags: 1
 // exact early exit against `best`, 2 record skip.  res_slot keeps kSlotAmbiguous /
