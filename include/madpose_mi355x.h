@@ -592,6 +592,99 @@ int mp_ransac_lo_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids,
 int mp_debug_ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts,
                              const int32_t *candidate, const int32_t *lo_rounds_accepted, const double *lo_score,
                              const int32_t *lo_counts, double *score, int32_t *out /* 7 */);
+/* mp_lsq_fit_set: one least-squares fit per entry on a random subset of the entry's inliers --
+ * LeastSquaresFit (rule MP_LSQ_RULE_LSQ) or the non-minimal fit of a local-optimisation step
+ * (MP_LSQ_RULE_NONMIN) of the estimators' LocalOptimization.  Entry e: models[e] (user units,
+ * in and out) of pair pair_ids[e] (NULL: pair e, num_entries = the pair count) -- a pair MAY
+ * occur in any number of entries; every entry has its own workspace slice and the pairs' list
+ * buffers are not touched -- with solver type solver_types[e] (0 MD, 1 point), threshold factor
+ * factors[e] (> 0, finite) and the subset streams streams[e] (0 .. 2^31 - 1), substreams[e]
+ * (0 .. 2^30 - 1).  Per entry:
+ *   1. the model goes to problem units as mp_refine_set takes it;
+ *   2. one sweep: score (mp_score_models' bits), num_inliers[t] = #(err_t < thr_t) and the wide
+ *      ascending lists err_t < thr_t * factor (one double product) of lengths num_wide[t] = M_t;
+ *   3. the size k.  With k_md = 3 / 4 / 4, k_pt = 5 / 6 / 7 (calibrated and scale only / shared /
+ *      two focal), ss = (k_md, k_md, 0) for solver type 0 and (0, 0, k_pt) for 1, mu =
+ *      min_sample_multiplicator, nu = non_min_sample_multiplier and M = sum M_t --
+ *      MP_LSQ_RULE_LSQ: any M_t < ss_t skips the entry, else k = mu * sum_t min(ss_t * mu, M_t);
+ *      MP_LSQ_RULE_NONMIN: k = max(35 calibrated / 36 otherwise, min(k_pt * nu, M / 2)), no skip;
+ *      64-bit products, clamped to M;
+ *   4. the subset: every element when M <= k, else the k smallest elements (t, i) in the order
+ *      (key, t, i), key = words 0 (high) and 1 of Philox4x32-10 with the counter (i, (substream
+ *      << 2) | t, pair index in the set, 0x80000000 | stream) and the key (seed low, seed high);
+ *      again three ascending lists, of lengths subset_sizes[t] = z_t (0 when the rule skipped);
+ *   5. mp_lm_refine_batch's size test on z: (z_0 < k_md && z_1 < k_md) || z_2 < k_pt;
+ *   6. either skip: status 3, the model's bytes unchanged;
+ *   7. otherwise mp_lm_refine_batch's problem on the three subset lists from the model, kind 0
+ *      (rule lsq) or 1 (rule nonmin), on the device LM: status 1 returns its model in user units
+ *      as mp_refine_set returns them, any other status the input bytes.
+ * subset_idx (nullable): mp_refine_set's inlier_idx layout over the entries (entry e's list t at
+ * 3 * (n of the entries before e) + t * n_e).  Entries run in runs whose wide lists total at
+ * most 2^26 ints (a run of one entry is always allowed); entry_chunk > 0 also bounds a run's
+ * entries; results depend on neither, nor on the other entries.  Two synchronisations per run.
+ * Variants 0 .. 3.  MP_EINVAL: null set; negative or more than 2^24 entries; rule not 0 / 1; a
+ * pair id outside the set; NULL pair_ids with num_entries != the pair count; a solver type,
+ * factor, stream or substream outside its range; negative entry_chunk; null arrays. */
+#define MP_LSQ_RULE_LSQ 0
+#define MP_LSQ_RULE_NONMIN 1
+typedef struct mp_lsq_fit_result {
+    double score;            /* of the input model */
+    int32_t num_inliers[3];  /* its tight counts */
+    int32_t num_wide[3];     /* the lengths of the wide lists */
+    int32_t subset_sizes[3]; /* the lengths of the subset's lists */
+    int32_t status;          /* 0 .. 3 as mp_lm_refine_batch */
+} mp_lsq_fit_result; /* 48 bytes */
+int mp_lsq_fit_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_ids /* nullable */,
+                   const int32_t *solver_types, const double *factors, int rule, uint64_t seed,
+                   const int32_t *streams, const int32_t *substreams, mp_model *models /* in/out */,
+                   mp_lsq_fit_result *results, int32_t *subset_idx /* nullable */, int64_t entry_chunk);
+/* Test hooks of the subset rule.  mp_debug_subset_select: the device kernel on three strictly
+ * ascending lists idx[offsets[t] .. offsets[t + 1]) (offsets[0] = 0, indices below 2^28) with
+ * the size k and the order (key & key_mask, t, i); the subset's list t to out_idx + offsets[t],
+ * its length to out_sizes[t].  Needs no pair set.  mp_debug_subset_select_host: the same through
+ * the host form of the rule (no device).  mp_debug_lsq_subset_size: the size rule of step 3 for
+ * the list lengths sizes[3]; *run = 0 when the rule skips the entry (*k = 0 then). */
+int mp_debug_subset_select(const int64_t offsets[4], const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                           int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx,
+                           int32_t out_sizes[3], int device);
+int mp_debug_subset_select_host(const int64_t offsets[4], const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                                int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx,
+                                int32_t out_sizes[3]);
+int mp_debug_lsq_subset_size(int rule, int solver_type, int variant, int32_t min_sample_multiplicator,
+                             int32_t non_min_sample_multiplier, const int32_t sizes[3], int64_t *k, int32_t *run);
+/* mp_ransac_lo_steps_set: mp_ransac_lo_set with the num_lo_steps steps of LocalOptimization
+ * after each local optimisation.  At a checkpoint, an entry whose minimal best was replaced
+ * (candidate c, solver type s) first does mp_ransac_lo_set's steps (1) and (2).  Then, with a
+ * the model step (2)'s mp_refine_relaxed_set returned (the minimal model's bytes if no round
+ * was accepted), Q = num_lsq_iterations (0 .. 254), lambda = threshold_multiplier and f_i =
+ * lambda - i * (lambda - 1) / (Q - 1) (Q >= 2; f_0 = lambda for Q = 1), step r = 0 .. lo_steps - 1
+ * runs the stages, each an mp_lsq_fit_set entry with stream = c, substream = 256 r + q:
+ *   q = 0:      (a, s, factor 1, MP_LSQ_RULE_NONMIN) -> m1; a status other than 1 ends the step;
+ *   q = 1:      (m1, s, factor 1, MP_LSQ_RULE_LSQ) -> m2;
+ *   q = 2 + i:  (m(2+i), s, factor f_i, MP_LSQ_RULE_LSQ) -> m(3+i), i = 0 .. Q - 1; a stage whose
+ *               status is not 1 passes its model on unchanged;
+ *   finals:     m(2+Q) of the entry's live steps, ranked by one mp_select_set in step order.
+ * All steps of all such entries go through a stage in one run: 2 + Q runs and one select per
+ * checkpoint.  A stage returns the score and counts of its input, so stages 1 .. 1 + Q score
+ * m1 .. m(1+Q); each is offered to the overall best (strict <), stage-major and in step order
+ * inside a stage, then the select's winner among the finals.  An accepted offer sets the
+ * overall best's score, model and counts, lo_index = c, lo_step = r and lo_stage = the stage
+ * that produced the model (q - 1 for the model stage q scored; 2 + Q for a final).  A later
+ * minimal model or local optimisation that becomes the overall best sets lo_step = lo_stage =
+ * -1 again.  The rule, the end of the call and the units are mp_ransac_lo_set's; with rounds =
+ * 0 the lists of an overall best that a step produced are mp_select_set's for that one model.
+ * MP_EINVAL: mp_ransac_lo_set's, lo_steps outside 1 .. 64, null steps_info, num_lsq_iterations
+ * outside 0 .. 254. */
+typedef struct mp_ransac_lo_steps_info {
+    int32_t lo_step, lo_stage;                /* the step and stage that gave the overall best; -1: none */
+    int32_t lo_step_offers, lo_step_accepted; /* the steps' offers / those that became the overall best */
+} mp_ransac_lo_steps_info; /* 16 bytes */
+int mp_ransac_lo_steps_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                           uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
+                           mp_model *models /* num_sel */, mp_ransac_result *results /* num_sel */,
+                           int32_t *inlier_idx /* nullable */, int32_t *stopped /* num_sel, nullable */,
+                           mp_ransac_lo_info *lo_info /* num_sel */, mp_ransac_lo_steps_info *steps_info /* num_sel */,
+                           int64_t sample_chunk, int64_t model_chunk);
 /* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
  * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
  * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the

@@ -180,6 +180,28 @@ class mp_ransac_lo_info(ctypes.Structure):
     ]
 
 
+class mp_lsq_fit_result(ctypes.Structure):
+    _fields_ = [
+        ("score", ctypes.c_double),
+        ("num_inliers", ctypes.c_int32 * 3),
+        ("num_wide", ctypes.c_int32 * 3),
+        ("subset_sizes", ctypes.c_int32 * 3),
+        ("status", ctypes.c_int32),
+    ]
+
+
+class mp_ransac_lo_steps_info(ctypes.Structure):
+    _fields_ = [
+        ("lo_step", ctypes.c_int32),
+        ("lo_stage", ctypes.c_int32),
+        ("lo_step_offers", ctypes.c_int32),
+        ("lo_step_accepted", ctypes.c_int32),
+    ]
+
+
+LSQ_RULES = {"lsq": 0, "nonmin": 1}
+LO_STEPS_MAX = 64
+
 EXPORTS = {
     "mp_select_batch": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
                                        c_double_p, c_double_p, c_double_p, ctypes.POINTER(mp_ransac_options),
@@ -228,6 +250,24 @@ EXPORTS = {
                                         ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                         ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
                                         c_int32_p, ctypes.POINTER(mp_ransac_lo_info), ctypes.c_int64, ctypes.c_int64]),
+    "mp_lsq_fit_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, c_int32_p, c_double_p, ctypes.c_int,
+                                      ctypes.c_uint64, c_int32_p, c_int32_p, ctypes.POINTER(mp_model),
+                                      ctypes.POINTER(mp_lsq_fit_result), c_int32_p, ctypes.c_int64]),
+    "mp_debug_subset_select": (ctypes.c_int, [c_int64_p, c_int32_p, ctypes.c_int64, ctypes.c_uint64, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, c_int32_p, c_int32_p,
+                                              ctypes.c_int]),
+    "mp_debug_subset_select_host": (ctypes.c_int, [c_int64_p, c_int32_p, ctypes.c_int64, ctypes.c_uint64,
+                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                                   c_int32_p, c_int32_p]),
+    "mp_debug_lsq_subset_size": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int32,
+                                                ctypes.c_int32, c_int32_p, c_int64_p, c_int32_p]),
+    "mp_ransac_lo_steps_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.POINTER(mp_model),
+                                              ctypes.POINTER(mp_ransac_result), c_int32_p, c_int32_p,
+                                              ctypes.POINTER(mp_ransac_lo_info),
+                                              ctypes.POINTER(mp_ransac_lo_steps_info), ctypes.c_int64,
+                                              ctypes.c_int64]),
     "mp_debug_ransac_lo_track": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_int32_p, c_int32_p, c_int32_p,
                                                 c_double_p, c_int32_p, c_double_p, c_int32_p]),
     "mp_debug_ransac_required": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_int32_p,

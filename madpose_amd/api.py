@@ -1297,6 +1297,83 @@ class PairSet:
         L.check(entry(h, ns, ptr, int(rounds), arr, res, idx.ctypes.data_as(L.c_int32_p)))
         return _refine_results(self.variant, arr, res, idx, offs)
 
+    def lsq_fit(self, models, solver_types, factor=1.0, rule="lsq", seed=0, streams=None, substreams=None,
+                pair_ids=None, with_subsets=False, entry_chunk=0):
+        """One least-squares fit per entry on a random subset of the entry's inliers
+        (mp_lsq_fit_set): the estimators' LeastSquaresFit (rule "lsq") or the non-minimal fit
+        of a local-optimisation step (rule "nonmin").  One entry per model; pair_ids (None: all
+        pairs in order) MAY repeat a pair.  solver_types: 0 (MD) or 1 (point) per entry, or one
+        value for all; factor: the thresholds' factor, a scalar or one value per entry; streams,
+        substreams: the subset's streams per entry (None: zeros; a scalar: for all).  Per
+        entry, a LsqFitResult: score and num_inliers of the given model (select's values),
+        num_wide (the inliers under the thresholds times factor), subset_sizes (the subset the
+        rule draws from those; sizes and rule: include/madpose_mi355x.h), status (3: the rule
+        or the solver's size test skipped the entry; else the LM's) and the model -- the LM's on
+        status 1, else the given one.  with_subsets: also the subset's three index lists."""
+        h = self._live()
+        if rule not in L.LSQ_RULES:
+            raise ValueError('rule must be "lsq" or "nonmin"')
+        if isinstance(entry_chunk, bool) or int(entry_chunk) != entry_chunk or entry_chunk < 0:
+            raise ValueError("entry_chunk must be a non-negative integer (0: the default)")
+        if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)) or not 0 <= seed < 1 << 64:
+            raise ValueError("seed must be an integer in 0 .. 2^64 - 1")
+        P = len(self._sizes)
+        ne = len(models)
+        if pair_ids is None:
+            if ne != P:
+                raise ValueError(f"one model per pair: {ne} for {P} pairs")
+            ids, ptr = None, None
+            sizes = list(self._sizes)
+        else:
+            ids = np.ascontiguousarray(np.asarray(pair_ids, dtype=np.int64).reshape(-1))
+            if len(ids) != ne:
+                raise ValueError(f"one model per entry: {ne} for {len(ids)} pair_ids")
+            for j, k in enumerate(ids.tolist()):
+                if not 0 <= k < P:
+                    raise ValueError(f"pair_ids[{j}] = {k} is outside the set of {P} pairs")
+            ids = ids.astype(np.int32)
+            ptr = ids.ctypes.data_as(L.c_int32_p)
+            sizes = [self._sizes[k] for k in ids.tolist()]
+        if ne == 0:
+            return []
+
+        def per_entry(val, name, dtype, lo, hi):
+            a = np.asarray(0 if val is None else val)
+            if a.dtype == np.bool_ or (dtype is np.int32 and not np.issubdtype(a.dtype, np.integer)):
+                raise ValueError(f"{name} must be integers")
+            a = np.ascontiguousarray(np.broadcast_to(a, (ne,)) if a.ndim == 0 else a.reshape(-1))
+            if len(a) != ne:
+                raise ValueError(f"one {name} value per entry: {len(a)} for {ne}")
+            if not (np.all(a >= lo) and np.all(a < hi)):
+                raise ValueError(f"{name} out of range")
+            return np.ascontiguousarray(a.astype(dtype))
+        st = per_entry(solver_types, "solver_types", np.int32, 0, 2)
+        sr = per_entry(streams, "streams", np.int32, 0, 1 << 31)
+        sb = per_entry(substreams, "substreams", np.int32, 0, 1 << 30)
+        fa = per_entry(factor, "factor", np.float64, np.nextafter(0.0, 1.0), np.inf)
+        offs = [0]
+        for n in sizes:
+            offs.append(offs[-1] + n)
+        arr = (L.mp_model * ne)(*[_model_to_c(m, self.variant) for m in models])
+        res = (L.mp_lsq_fit_result * ne)()
+        idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32) if with_subsets else None
+        L.check(L.lib().mp_lsq_fit_set(h, ne, ptr, st.ctypes.data_as(L.c_int32_p), _dp(fa), L.LSQ_RULES[rule],
+                                       int(seed), sr.ctypes.data_as(L.c_int32_p), sb.ctypes.data_as(L.c_int32_p),
+                                       arr, res, None if idx is None else idx.ctypes.data_as(L.c_int32_p),
+                                       int(entry_chunk)))
+        out = []
+        for e in range(ne):
+            q, n = res[e], sizes[e]
+            r = LsqFitResult()
+            r.score, r.status = float(q.score), int(q.status)
+            r.num_inliers, r.num_wide, r.subset_sizes = list(q.num_inliers), list(q.num_wide), list(q.subset_sizes)
+            r.model_row = np.frombuffer(bytes(arr[e]), dtype=np.float64).copy()
+            r.model = _model_from_c(arr[e], self.variant)
+            if idx is not None:
+                base = 3 * offs[e]
+                r.subsets = [idx[base + t * n: base + t * n + q.subset_sizes[t]].copy() for t in range(3)]
+            out.append(r)
+        return out
 
     def _check_draw(self, budget, seed, point_share, ns):
         if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) or budget < 0:
@@ -1365,7 +1442,7 @@ class PairSet:
                  slot[moffs[j]:moffs[j + 1]].copy()) for j in range(ns)]
 
     def ransac(self, budget=None, seed=0, point_share=None, samples=None, rounds=3, pair_ids=None, sample_chunk=0,
-               model_chunk=0, step=None, lo=None):
+               model_chunk=0, step=None, lo=None, lo_steps=None):
         """Fixed-budget RANSAC on the selected pairs in one call (mp_ransac_set): draw ->
         hypothesize -> select -> refine on the device-resident pairs.  Exactly one of budget
         (samples drawn on the device as draw(budget, seed, point_share) draws them) and samples
@@ -1393,10 +1470,30 @@ class PairSet:
         model, score_initial, score_final, rounds_*, status and inlier_indices the refined
         overall best.  lo_runs, lo_accepted: the pair's local optimisations and how many of
         them became the overall best; lo_index: the candidate whose local optimisation gave
-        the overall best (-1: it is a minimal model)."""
+        the overall best (-1: it is a minimal model).
+
+        lo_steps (None, or an integer in 1..64; needs lo): the estimators' LO steps after each
+        local optimisation (mp_ransac_lo_steps_set).  From the model a that refine(relax=True,
+        rounds=lo) returned for candidate c of solver type s, step r = 0 .. lo_steps - 1 runs
+        lsq_fit(a, s, rule="nonmin") -> m1 (a status other than 1 ends the step), lsq_fit(m1, s,
+        rule="lsq") -> m2, then num_lsq_iterations fits lsq_fit(m, s, factor=f_i, rule="lsq") with
+        f_i = t - i (t - 1) / (Q - 1) falling from t = threshold_multiplier to 1, each with
+        streams=c and substreams=256 r + stage; the steps' last models are ranked by one select.
+        Every model a stage scored (each lsq_fit scores its input) and the select's winner are
+        offered to the overall best, strictly lower score wins.  All steps of all pairs of a
+        checkpoint go through a stage in one launch sequence.  lo_step, lo_stage: the step and
+        the stage that produced the overall best (-1: no step did; lo_stage is 2 +
+        num_lsq_iterations for a step's last model); lo_step_offers, lo_step_accepted: the
+        offers made and those that became the overall best."""
         h = self._live()
         if self._hyp_error:
             raise ValueError(self._hyp_error.replace("hypothesize", "ransac"))
+        if lo_steps is not None:
+            if (isinstance(lo_steps, bool) or not isinstance(lo_steps, (int, np.integer))
+                    or not 1 <= lo_steps <= L.LO_STEPS_MAX):
+                raise ValueError("lo_steps must be None (no LO steps) or an integer in 1..64")
+            if lo is None:
+                raise ValueError("lo_steps needs lo: the steps start from a local optimisation's model")
         if lo is not None:
             if isinstance(lo, bool) or not isinstance(lo, (int, np.integer)) or not 1 <= lo <= 64:
                 raise ValueError("lo must be None (no local optimisation) or an integer in 1..64")
@@ -1440,8 +1537,15 @@ class PairSet:
         res = (L.mp_ransac_result * ns)()
         idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
         stopped = np.zeros(ns, dtype=np.int32)
-        info = None
-        if lo is not None:
+        info = sinfo = None
+        if lo is not None and lo_steps is not None:
+            info = (L.mp_ransac_lo_info * ns)()
+            sinfo = (L.mp_ransac_lo_steps_info * ns)()
+            L.check(L.lib().mp_ransac_lo_steps_set(h, ns, ptr, budget, int(step), seed, share, int(rounds), int(lo),
+                                                   int(lo_steps), arr, res, idx.ctypes.data_as(L.c_int32_p),
+                                                   stopped.ctypes.data_as(L.c_int32_p), info, sinfo,
+                                                   int(sample_chunk), int(model_chunk)))
+        elif lo is not None:
             info = (L.mp_ransac_lo_info * ns)()
             L.check(L.lib().mp_ransac_lo_set(h, ns, ptr, budget, int(step), seed, share, int(rounds), int(lo), arr,
                                              res, idx.ctypes.data_as(L.c_int32_p),
@@ -1464,6 +1568,10 @@ class PairSet:
             if info is not None:
                 r.lo_runs, r.lo_accepted, r.lo_index = (int(info[j].lo_runs), int(info[j].lo_accepted),
                                                         int(info[j].lo_index))
+            if sinfo is not None:
+                r.lo_step, r.lo_stage = int(sinfo[j].lo_step), int(sinfo[j].lo_stage)
+                r.lo_step_offers, r.lo_step_accepted = (int(sinfo[j].lo_step_offers),
+                                                        int(sinfo[j].lo_step_accepted))
             r.index, r.sample, r.slot, r.solver_type = (int(q.best_candidate), int(q.best_sample), int(q.best_slot),
                                                         int(q.best_type))
             r.score_selected = float(q.score_selected)
@@ -1478,6 +1586,27 @@ class PairSet:
         return out
 
 
+class LsqFitResult:
+    """One entry's outcome of PairSet.lsq_fit: score and num_inliers (of the given model),
+    num_wide, subset_sizes, status (3: skipped; else the LM's: 1 refined), model and model_row
+    (user units: the LM's on status 1, else the given model's bytes), subsets (with_subsets
+    only: the subset's three int32 index arrays; None otherwise)."""
+
+    def __init__(self):
+        self.score = 0.0
+        self.num_inliers = [0, 0, 0]
+        self.num_wide = [0, 0, 0]
+        self.subset_sizes = [0, 0, 0]
+        self.status = -1
+        self.model = None
+        self.model_row = np.zeros(17)
+        self.subsets = None
+
+    def __repr__(self):
+        return (f"LsqFitResult(score {self.score:.6g}, inliers={self.num_inliers}, wide={self.num_wide}, "
+                f"subset={self.subset_sizes}, status={self.status})")
+
+
 class RansacResult:
     """One pair's outcome of PairSet.ransac: num_samples, num_candidates; index (the winner
     among the pair's candidates; -1: none), sample and slot (its origin), solver_type (0 the
@@ -1489,13 +1618,18 @@ class RansacResult:
     model's); norm_scale; stopped (the adaptive mode only: the termination rule ended the
     pair before its budget; False otherwise); lo_runs, lo_accepted, lo_index (ransac(lo=...)
     only: local optimisations run, those that became the overall best, and the candidate
-    whose local optimisation gave the returned start model; 0, 0 and -1 otherwise)."""
+    whose local optimisation gave the returned start model; 0, 0 and -1 otherwise); lo_step,
+    lo_stage, lo_step_offers, lo_step_accepted (ransac(lo_steps=...) only: the LO step and stage
+    that produced the returned start model, -1 when no step did, and the steps' offers to the
+    overall best and those accepted; -1, -1, 0 and 0 otherwise)."""
 
     def __init__(self):
         self.num_samples = self.num_candidates = 0
         self.stopped = False
         self.lo_runs = self.lo_accepted = 0
         self.lo_index = -1
+        self.lo_step = self.lo_stage = -1
+        self.lo_step_offers = self.lo_step_accepted = 0
         self.index = self.sample = self.slot = self.solver_type = -1
         self.score_selected = self.score_initial = self.score_final = float(np.finfo(np.float64).max)
         self.rounds_run = self.rounds_accepted = 0

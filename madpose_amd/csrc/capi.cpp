@@ -9,6 +9,7 @@
 
 #include "../../include/madpose_mi355x.h"
 #include "host/engine.h"
+#include "include/mp_subset.h"
 #include "host/hypothesis_plan.h"
 #include "host/pair_set_plan.h"
 #include "host/rng.h"
@@ -437,6 +438,66 @@ int mp_ransac_lo_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids,
                           rounds, lo_rounds, reinterpret_cast<mp::Model *>(models),
                           reinterpret_cast<mp::RansacResult *>(results), inlier_idx, stopped,
                           reinterpret_cast<mp::RansacLoInfo *>(lo_info), sample_chunk, model_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_lsq_fit_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_ids, const int32_t *solver_types,
+                   const double *factors, int rule, uint64_t seed, const int32_t *streams, const int32_t *substreams,
+                   mp_model *models, mp_lsq_fit_result *results, int32_t *subset_idx, int64_t entry_chunk) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::LsqFitResult) == sizeof(mp_lsq_fit_result) && sizeof(mp_lsq_fit_result) == 48,
+                      "lsq fit result layout");
+        static_assert(mp::kSubsetLsq == MP_LSQ_RULE_LSQ && mp::kSubsetNonmin == MP_LSQ_RULE_NONMIN, "lsq rules");
+        mp::lsq_fit_set(reinterpret_cast<mp::PairSet *>(set), num_entries, pair_ids, solver_types, factors, rule, seed,
+                        streams, substreams, reinterpret_cast<mp::Model *>(models),
+                        reinterpret_cast<mp::LsqFitResult *>(results), subset_idx, entry_chunk);
+        return MP_OK;
+    });
+}
+
+int mp_debug_subset_select(const int64_t offsets[4], const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                           int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx,
+                           int32_t out_sizes[3], int device) {
+    return guarded([&]() {
+        mp::subset_select_device(offsets, idx, k, seed, pair, stream, substream, key_mask, out_idx, out_sizes, device);
+        return MP_OK;
+    });
+}
+
+int mp_debug_subset_select_host(const int64_t offsets[4], const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                                int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx,
+                                int32_t out_sizes[3]) {
+    return guarded([&]() {
+        mp::subset_select_host_hook(offsets, idx, k, seed, pair, stream, substream, key_mask, out_idx, out_sizes);
+        return MP_OK;
+    });
+}
+
+int mp_debug_lsq_subset_size(int rule, int solver_type, int variant, int32_t min_sample_multiplicator,
+                             int32_t non_min_sample_multiplier, const int32_t sizes[3], int64_t *k, int32_t *run) {
+    return guarded([&]() {
+        if (!run) throw std::invalid_argument("null run");
+        *run = mp::lsq_subset_size(rule, solver_type, variant, min_sample_multiplicator, non_min_sample_multiplier,
+                                   sizes, k);
+        return MP_OK;
+    });
+}
+
+int mp_ransac_lo_steps_set(mp_pair_set *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                           uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
+                           mp_model *models, mp_ransac_result *results, int32_t *inlier_idx, int32_t *stopped,
+                           mp_ransac_lo_info *lo_info, mp_ransac_lo_steps_info *steps_info, int64_t sample_chunk,
+                           int64_t model_chunk) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::RansacLoStepsInfo) == sizeof(mp_ransac_lo_steps_info) &&
+                          sizeof(mp_ransac_lo_steps_info) == 16,
+                      "lo steps info layout");
+        mp::ransac_lo_steps_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, budget, step, seed,
+                                point_share, rounds, lo_rounds, lo_steps, reinterpret_cast<mp::Model *>(models),
+                                reinterpret_cast<mp::RansacResult *>(results), inlier_idx, stopped,
+                                reinterpret_cast<mp::RansacLoInfo *>(lo_info),
+                                reinterpret_cast<mp::RansacLoStepsInfo *>(steps_info), sample_chunk, model_chunk);
         return MP_OK;
     });
 }

@@ -49,7 +49,9 @@
 #include "env.h"
 #include "hypothesis_plan.h"
 #include "lo_sweep.h"
+#include "lsq_fit_plan.h"
 #include "pair_set_plan.h"
+#include "ransac_lo_steps.h"
 #include "ransac_lo_track.h"
 #include "ransac_stop.h"
 #include "refine_plan.h"
@@ -2763,6 +2765,178 @@ void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
     MP_HIP(hipStreamSynchronize(stream));
 }
 
+// lsq_fit_run's device arrays: grown to the largest run seen, so the stages of one
+// ransac_lo_steps_set checkpoint (and the runs of one call) share them
+struct LsqBuffers {
+    size_t cap = 0, ws_cap = 0;
+    std::unique_ptr<DevArray<LsqEntry>> d_entries;
+    std::unique_ptr<DevArray<ScoreRec>> d_recs;
+    std::unique_ptr<DevArray<LsqOut>> d_out;
+    std::unique_ptr<DevArray<LmJob>> d_jobs;
+    std::unique_ptr<DevArray<LmPairRef>> d_refs;
+    std::unique_ptr<DevArray<Model>> d_models;
+    std::unique_ptr<DevArray<int>> d_status;
+    std::unique_ptr<DevArray<int>> d_ws;
+    void ensure(size_t entries, size_t ws_ints) {
+        if (entries > cap) {
+            d_entries.reset(), d_recs.reset(), d_out.reset(), d_jobs.reset();
+            d_refs.reset(), d_models.reset(), d_status.reset();
+            d_entries.reset(new DevArray<LsqEntry>(entries));
+            d_recs.reset(new DevArray<ScoreRec>(entries));
+            d_out.reset(new DevArray<LsqOut>(entries));
+            d_jobs.reset(new DevArray<LmJob>(entries));
+            d_refs.reset(new DevArray<LmPairRef>(entries));
+            d_models.reset(new DevArray<Model>(entries));
+            d_status.reset(new DevArray<int>(entries));
+            cap = entries;
+        }
+        if (ws_ints > ws_cap || !d_ws) {
+            d_ws.reset(); // (free first)
+            d_ws.reset(new DevArray<int>(ws_ints));
+            ws_cap = ws_ints;
+        }
+    }
+};
+
+// One least-squares fit on a random subset of each entry's inliers (the body of
+// mp_lsq_fit_set; the stages of ransac_lo_steps_set).  Entry e: model models[e] (user units,
+// in and out) of pair pair_ids[e] (null: e) of the resident pairs -- a pair may occur in any
+// number of entries, each has its own workspace slice and the pairs' list buffers are not
+// touched.  Per run of entries (host/lsq_fit_plan.h): the records prepared on the host
+// (prepare_score_rec: mp_score_models' bits), launch_lsq_sweep and launch_lsq_subset, the
+// counts back (the first synchronisation); the rule's skip and mp_lm_refine_batch's size test
+// on the subset's sizes (either: status 3, the model's bytes kept); make_lm_job on the subset's
+// sizes (kind 1 for the rule kSubsetNonmin) with the lists in the entry's slice, one
+// launch_lm_pairs, models and statuses back (the second).  Status 1: the LM's model in user
+// units, as refine_run returns them; any other status keeps the input bytes.  subset_idx
+// (nullable): entry e's subset lists to subset_idx + 3 out_off[e] + t n_e.
+void lsq_fit_run(ResidentPairs &R, hipStream_t stream, const RansacOptions &opts, const EstimatorConfig &cfg,
+                 int32_t ne, const int32_t *pair_ids, const int32_t *solver_types, const double *factors, int rule,
+                 uint64_t seed, const int32_t *streams, const int32_t *substreams, Model *models,
+                 LsqFitResult *results, int32_t *subset_idx, const int64_t *out_off, int64_t entry_chunk,
+                 LsqBuffers &B) {
+    if (ne <= 0) return;
+    const int variant = R.variant, v = R.v;
+    const int kmd = v == kCal ? 3 : 4, kpt = v == kCal ? 5 : (v == kSF ? 6 : 7);
+    const std::vector<PairConst> &Ch = R.Ch;
+    auto pair_of = [&](int32_t e) { return pair_ids ? pair_ids[e] : e; };
+    std::vector<int64_t> ns((size_t)ne);
+    for (int32_t e = 0; e < ne; ++e) ns[(size_t)e] = R.n[(size_t)pair_of(e)];
+    std::vector<LsqEntry> entries;
+    std::vector<ScoreRec> recs;
+    std::vector<LsqOut> outs;
+    std::vector<Model> cur, lm_out;
+    std::vector<LmJob> jobs;
+    std::vector<LmPairRef> refs;
+    std::vector<int> which, st;
+    for (const LsqRun &run : lsq_fit_runs(ne, ns.data(), entry_chunk)) {
+        const size_t m = (size_t)(run.e1 - run.e0);
+        entries.resize(m);
+        recs.resize(m);
+        outs.resize(m);
+        cur.resize(m);
+        int64_t ws_ints = 0;
+        for (size_t i = 0; i < m; ++i) {
+            const int32_t e = run.e0 + (int32_t)i;
+            const int k = pair_of(e);
+            cur[i] = models[e];
+            if (variant == kSF || variant == kTF) {
+                cur[i].focal0 /= R.norm_scale[(size_t)k];
+                cur[i].focal1 /= R.norm_scale[(size_t)k];
+            }
+            LsqEntry &E = entries[i];
+            E.pair = k;
+            E.stype = solver_types[e];
+            E.rule = rule;
+            E.k = 0;
+            E.stream = (uint32_t)streams[e];
+            E.substream = (uint32_t)substreams[e];
+            E.stride = (int)ns[(size_t)e];
+            E.pad = 0;
+            E.ws_off = ws_ints;
+            E.factor = factors[e];
+            ws_ints += 6 * ns[(size_t)e];
+            prepare_score_rec(Ch[(size_t)k], cur[i], recs[i]);
+        }
+        B.ensure(m, (size_t)ws_ints);
+        MP_HIP(hipMemcpyAsync(B.d_entries->p, entries.data(), sizeof(LsqEntry) * m, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(B.d_recs->p, recs.data(), sizeof(ScoreRec) * m, hipMemcpyHostToDevice, stream));
+        MP_HIP(launch_lsq_sweep(stream, v, R.d_D.p, R.d_C.p, B.d_entries->p, B.d_recs->p, (int)m, B.d_ws->p,
+                                B.d_out->p));
+        MP_HIP(launch_lsq_subset(stream, B.d_entries->p, (int)m, B.d_ws->p, B.d_out->p, v,
+                                 opts.min_sample_multiplicator, opts.non_min_sample_multiplier, seed, kSubsetMaskAll));
+        MP_HIP(hipMemcpyAsync(outs.data(), B.d_out->p, sizeof(LsqOut) * m, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+        jobs.clear();
+        refs.clear();
+        which.clear();
+        for (size_t i = 0; i < m; ++i) {
+            const int32_t e = run.e0 + (int32_t)i;
+            const int k = pair_of(e);
+            const LsqOut &O = outs[i];
+            LsqFitResult &Q = results[e];
+            Q.score = O.score;
+            for (int t = 0; t < 3; ++t) {
+                Q.num_inliers[t] = O.tight[t];
+                Q.num_wide[t] = O.wide[t];
+                Q.subset_sizes[t] = O.sub[t];
+            }
+            Q.status = 3;
+            const int *sz = O.sub;
+            // skipped by the rule, or too few data for the solver (the size test of least_squares)
+            if (O.k < 0 || (sz[0] < kmd && sz[1] < kmd) || sz[2] < kpt) continue;
+            LmJob J = make_lm_job(R.Ps[(size_t)k], cfg, sz, 0, rule == kSubsetNonmin, cur[i]);
+            // (the lists of a slice lie n apart, not back to back)
+            J.off1 = (int)ns[(size_t)e];
+            J.off2 = 2 * (int)ns[(size_t)e];
+            jobs.push_back(J);
+            LmPairRef ref;
+            ref.pair = k;
+            ref.pad = 0;
+            ref.idx_off = entries[i].ws_off + 3 * ns[(size_t)e];
+            refs.push_back(ref);
+            which.push_back((int)i);
+        }
+        const size_t nj = jobs.size();
+        if (nj > 0) {
+            lm_out.resize(nj);
+            st.resize(nj);
+            MP_HIP(hipMemcpyAsync(B.d_jobs->p, jobs.data(), sizeof(LmJob) * nj, hipMemcpyHostToDevice, stream));
+            MP_HIP(hipMemcpyAsync(B.d_refs->p, refs.data(), sizeof(LmPairRef) * nj, hipMemcpyHostToDevice, stream));
+            MP_HIP(launch_lm_pairs(stream, v, R.d_D.p, R.d_C.p, B.d_jobs->p, B.d_refs->p, (int)nj, B.d_ws->p,
+                                   B.d_models->p, B.d_status->p));
+            MP_HIP(hipMemcpyAsync(lm_out.data(), B.d_models->p, sizeof(Model) * nj, hipMemcpyDeviceToHost, stream));
+            MP_HIP(hipMemcpyAsync(st.data(), B.d_status->p, sizeof(int) * nj, hipMemcpyDeviceToHost, stream));
+        }
+        if (subset_idx)
+            for (size_t i = 0; i < m; ++i) {
+                const int32_t e = run.e0 + (int32_t)i;
+                const int64_t n = ns[(size_t)e];
+                for (int t = 0; t < 3; ++t)
+                    if (outs[i].sub[t] > 0)
+                        MP_HIP(hipMemcpyAsync(subset_idx + 3 * out_off[e] + t * n,
+                                              B.d_ws->p + entries[i].ws_off + (3 + t) * n,
+                                              sizeof(int) * (size_t)outs[i].sub[t], hipMemcpyDeviceToHost, stream));
+            }
+        MP_HIP(hipStreamSynchronize(stream));
+        for (size_t q = 0; q < nj; ++q) {
+            const int32_t e = run.e0 + which[q];
+            results[e].status = st[q];
+            if (st[q] != 1) continue; // (the input bytes stay)
+            const double norm = R.norm_scale[(size_t)pair_of(e)];
+            Model mo = lm_out[q];
+            if (variant == kSF) {
+                mo.focal0 *= norm;
+                mo.focal1 = mo.focal0;
+            } else if (variant == kTF) {
+                mo.focal0 *= norm;
+                mo.focal1 *= norm;
+            }
+            models[e] = mo;
+        }
+    }
+}
+
 // the argument checks refine_batch and the pair set's creation share (all before any array
 // is read beyond offsets, and before the device is touched)
 void check_pair_arrays(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
@@ -3625,6 +3799,122 @@ void refine_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int roun
                relax, set->opts.threshold_multiplier);
 }
 
+void lsq_fit_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, const int32_t *solver_types,
+                 const double *factors, int rule, uint64_t seed, const int32_t *streams, const int32_t *substreams,
+                 Model *models, LsqFitResult *results, int32_t *subset_idx, int64_t entry_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_lsq_entries(set->num_pairs, num_entries, pair_ids, solver_types, factors, rule, streams, substreams,
+                      entry_chunk);
+    if (num_entries == 0) return;
+    if (!models || !results) throw std::invalid_argument("null models or results");
+    ResidentPairs &R = *set->R;
+    std::vector<int64_t> out_off((size_t)num_entries + 1, 0);
+    for (int32_t e = 0; e < num_entries; ++e)
+        out_off[(size_t)e + 1] = out_off[(size_t)e] + R.n[(size_t)(pair_ids ? pair_ids[e] : e)];
+    CtxLease lease(set->device);
+    LsqBuffers B;
+    lsq_fit_run(R, lease.c->stream, set->opts, set->cfg, num_entries, pair_ids, solver_types, factors, rule, seed,
+                streams, substreams, models, results, subset_idx, out_off.data(), entry_chunk, B);
+}
+
+namespace {
+void check_subset_lists(const int64_t *offsets, const int32_t *idx, int64_t k, int32_t pair, int32_t stream,
+                        int32_t substream, const int32_t *out_sizes) {
+    if (!offsets || !out_sizes) throw std::invalid_argument("null offsets or sizes");
+    if (offsets[0] != 0) throw std::invalid_argument("offsets must start at 0");
+    for (int t = 0; t < 3; ++t) {
+        if (offsets[t + 1] < offsets[t]) throw std::invalid_argument("offsets must not decrease");
+        if (offsets[t + 1] - offsets[t] > (int64_t)kSubsetIndexMax) throw std::invalid_argument("list too long");
+    }
+    if (offsets[3] > 0 && !idx) throw std::invalid_argument("null idx");
+    for (int t = 0; t < 3; ++t)
+        for (int64_t j = offsets[t]; j < offsets[t + 1]; ++j) {
+            if (idx[j] < 0 || (uint32_t)idx[j] >= kSubsetIndexMax)
+                throw std::invalid_argument("index outside 0 .. 2^28 - 1");
+            if (j > offsets[t] && idx[j] <= idx[j - 1]) throw std::invalid_argument("lists must ascend strictly");
+        }
+    if (k < 0 || k > INT32_MAX) throw std::invalid_argument("k must be in 0 .. 2^31 - 1");
+    if (pair < 0 || stream < 0 || substream < 0 || (uint32_t)substream >= kSubsetSubstreamMax)
+        throw std::invalid_argument("pair, stream or substream out of range");
+}
+} // namespace
+
+void subset_select_host_hook(const int64_t *offsets, const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                             int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx,
+                             int32_t *out_sizes) {
+    check_subset_lists(offsets, idx, k, pair, stream, substream, out_sizes);
+    const int *lists[3] = {idx + offsets[0], idx + offsets[1], idx + offsets[2]};
+    const int M[3] = {(int)(offsets[1] - offsets[0]), (int)(offsets[2] - offsets[1]), (int)(offsets[3] - offsets[2])};
+    std::vector<int> out[3];
+    subset_select_host(lists, M, k, seed, (uint32_t)pair, (uint32_t)stream, (uint32_t)substream, key_mask, out);
+    for (int t = 0; t < 3; ++t) {
+        out_sizes[t] = (int32_t)out[t].size();
+        if (!out[t].empty()) {
+            if (!out_idx) throw std::invalid_argument("null output");
+            std::copy(out[t].begin(), out[t].end(), out_idx + offsets[t]);
+        }
+    }
+}
+
+void subset_select_device(const int64_t *offsets, const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                          int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx, int32_t *out_sizes,
+                          int device) {
+    check_subset_lists(offsets, idx, k, pair, stream, substream, out_sizes);
+    if (offsets[3] > 0 && !out_idx) throw std::invalid_argument("null output");
+    // one entry whose three lists lie `stride` apart, as lsq_sweep_kernel leaves them
+    int64_t stride = 1;
+    for (int t = 0; t < 3; ++t) stride = std::max(stride, offsets[t + 1] - offsets[t]);
+    CtxLease lease(device);
+    hipStream_t s = lease.c->stream;
+    DevArray<int> d_ws((size_t)(6 * stride));
+    DevArray<LsqEntry> d_entry(1);
+    DevArray<LsqOut> d_out(1);
+    LsqEntry E;
+    std::memset(&E, 0, sizeof(E));
+    E.pair = pair;
+    E.rule = -1;
+    E.k = (int)k;
+    E.stream = (uint32_t)stream;
+    E.substream = (uint32_t)substream;
+    E.stride = (int)stride;
+    E.factor = 1.0;
+    LsqOut O;
+    std::memset(&O, 0, sizeof(O));
+    for (int t = 0; t < 3; ++t) {
+        O.wide[t] = (int)(offsets[t + 1] - offsets[t]);
+        if (O.wide[t] > 0)
+            MP_HIP(hipMemcpyAsync(d_ws.p + t * stride, idx + offsets[t], sizeof(int) * (size_t)O.wide[t],
+                                  hipMemcpyHostToDevice, s));
+    }
+    MP_HIP(hipMemcpyAsync(d_entry.p, &E, sizeof(E), hipMemcpyHostToDevice, s));
+    MP_HIP(hipMemcpyAsync(d_out.p, &O, sizeof(O), hipMemcpyHostToDevice, s));
+    MP_HIP(launch_lsq_subset(s, d_entry.p, 1, d_ws.p, d_out.p, 0, 1, 1, seed, key_mask));
+    MP_HIP(hipMemcpyAsync(&O, d_out.p, sizeof(O), hipMemcpyDeviceToHost, s));
+    MP_HIP(hipStreamSynchronize(s));
+    for (int t = 0; t < 3; ++t) {
+        out_sizes[t] = O.sub[t];
+        if (O.sub[t] < 0 || O.sub[t] > O.wide[t]) throw std::logic_error("subset_select: a size outside its list");
+        if (O.sub[t] > 0)
+            MP_HIP(hipMemcpyAsync(out_idx + offsets[t], d_ws.p + (3 + t) * stride, sizeof(int) * (size_t)O.sub[t],
+                                  hipMemcpyDeviceToHost, s));
+    }
+    MP_HIP(hipStreamSynchronize(s));
+}
+
+int lsq_subset_size(int rule, int solver_type, int variant, int mu, int nu, const int32_t *sizes, int64_t *k) {
+    if (rule != kSubsetLsq && rule != kSubsetNonmin) throw std::invalid_argument("rule must be 0 (lsq) or 1 (nonmin)");
+    if (solver_type != 0 && solver_type != 1) throw std::invalid_argument("solver_type must be 0 or 1");
+    if (variant < 0 || variant > 3) throw std::invalid_argument("variant must be in 0..3");
+    if (!sizes || !k) throw std::invalid_argument("null sizes or k");
+    for (int t = 0; t < 3; ++t)
+        if (sizes[t] < 0 || (uint32_t)sizes[t] > kSubsetIndexMax)
+            throw std::invalid_argument("sizes must be in 0 .. 2^28");
+    if (mu < 0 || nu < 0) throw std::invalid_argument("negative multiplier");
+    const int M[3] = {sizes[0], sizes[1], sizes[2]};
+    return subset_size(rule, solver_type, variant == kScaleOnly ? kCal : variant, mu, nu, M, k) ? 1 : 0;
+}
+
 void select_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
                 const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
                 int64_t model_chunk) {
@@ -4184,10 +4474,12 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
 }
 
-void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
+namespace {
+// ransac_lo_set (lo_steps = 0: its launches and its bytes) and ransac_lo_steps_set
+void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk) {
+                   int64_t model_chunk, int32_t lo_steps, RansacLoStepsInfo *steps_info) {
     if (!set) throw std::invalid_argument("null pair set");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (lo_rounds < 1 || lo_rounds > 64) throw std::invalid_argument("lo_rounds must be in 1..64");
@@ -4220,6 +4512,7 @@ void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
     // them; the overall best: track[j] (host/ransac_lo_track.h) and models[j] (user units)
     std::vector<Model> minimal((size_t)num_sel);
     std::vector<LoTrack> track((size_t)num_sel);
+    std::vector<LoStepTrack> strack((size_t)num_sel); // (lo_steps > 0: what the steps gave)
     std::vector<int64_t> drawn(2 * (size_t)num_sel, 0);
     std::vector<int> active; // the entries still sampling, in selection order
     for (int j = 0; j < num_sel; ++j) {
@@ -4262,6 +4555,16 @@ void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
         std::vector<int> next, lo_j;
         std::vector<Model> lo_models;
         std::vector<RefineResult> lo_res;
+        // the steps: the live steps' entry (index into lo_j), step and current model, a stage's
+        // arguments and results, and the finals' select
+        LsqBuffers lsq_bufs;
+        std::vector<int> st_i, st_r, fin_first;
+        std::vector<Model> st_m, st_in;
+        std::vector<int32_t> st_ids, st_types, st_streams, st_sub, fin_ids;
+        std::vector<double> st_fac;
+        std::vector<LsqFitResult> st_res;
+        std::vector<int64_t> fin_off, fin_moff;
+        std::vector<SelectResult> fin_res;
         while (!active.empty()) {
             const int na = (int)active.size();
             ids.resize((size_t)na);
@@ -4312,6 +4615,7 @@ void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                     Q.score_selected = W.best_score;
                     minimal[(size_t)j] = co.models[(size_t)(cp.moff[(size_t)a] + W.best_index)];
                     if (lo_take_minimal(track[(size_t)j], W.best_score, W.num_inliers)) {
+                        lo_step_clear(strack[(size_t)j]);
                         models[j] = minimal[(size_t)j];
                         take_lists(j, W.num_inliers);
                     }
@@ -4335,8 +4639,86 @@ void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                     const RefineResult &F = lo_res[(size_t)i];
                     if (lo_take_refined(track[(size_t)j], results[j].best_candidate, F.rounds_accepted, F.score_final,
                                         F.num_inliers)) {
+                        lo_step_clear(strack[(size_t)j]);
                         models[j] = lo_models[(size_t)i];
                         take_lists(j, F.num_inliers);
+                    }
+                }
+                // ---- the LO steps (host/ransac_lo_steps.h): every step of every such entry goes
+                // through each stage in one lsq_fit_run, then one select over the finals ----
+                if (lo_steps > 0) {
+                    const int Q = set->opts.num_lsq_iterations;
+                    const double lambda = set->opts.threshold_multiplier;
+                    // the live steps, entry-major in step order: (i, r) and the step's current model
+                    st_i.clear(), st_r.clear(), st_m.clear();
+                    for (int i = 0; i < nl; ++i)
+                        for (int r = 0; r < lo_steps; ++r) {
+                            st_i.push_back(i);
+                            st_r.push_back(r);
+                            st_m.push_back(lo_models[(size_t)i]); // (a: what the relaxed refinement returned)
+                        }
+                    for (int q = 0; q <= 1 + Q && !st_i.empty(); ++q) {
+                        const size_t m = st_i.size();
+                        st_ids.resize(m), st_types.resize(m), st_streams.resize(m), st_sub.resize(m);
+                        st_res.resize(m);
+                        st_fac.assign(m, q < 2 ? 1.0 : lo_step_factor(q - 2, Q, lambda));
+                        st_in = st_m;
+                        for (size_t e = 0; e < m; ++e) {
+                            const int j = lo_j[(size_t)st_i[e]];
+                            st_ids[e] = sel[j];
+                            st_types[e] = results[j].best_type;
+                            st_streams[e] = results[j].best_candidate;
+                            st_sub[e] = lo_step_substream(st_r[e], q);
+                        }
+                        lsq_fit_run(R, stream, set->opts, set->cfg, (int32_t)m, st_ids.data(), st_types.data(),
+                                    st_fac.data(), q == 0 ? kSubsetNonmin : kSubsetLsq, seed, st_streams.data(),
+                                    st_sub.data(), st_m.data(), st_res.data(), nullptr, nullptr, 0, lsq_bufs);
+                        if (q == 0) { // a step whose non-minimal fit gave no model ends and offers nothing
+                            size_t w = 0;
+                            for (size_t e = 0; e < m; ++e) {
+                                if (st_res[e].status != 1) continue;
+                                st_i[w] = st_i[e], st_r[w] = st_r[e], st_m[w] = st_m[e];
+                                ++w;
+                            }
+                            st_i.resize(w), st_r.resize(w), st_m.resize(w);
+                            continue;
+                        }
+                        // the stage scored its input, the model stage q - 1 produced: offered in step order
+                        for (size_t e = 0; e < m; ++e) {
+                            const int j = lo_j[(size_t)st_i[e]];
+                            if (lo_step_offer(track[(size_t)j], strack[(size_t)j], results[j].best_candidate, st_r[e],
+                                              q - 1, st_res[e].score, st_res[e].num_inliers))
+                                models[j] = st_in[e];
+                        }
+                    }
+                    // the finals: one select over each entry's live steps' last models, in step order
+                    if (!st_i.empty()) {
+                        fin_ids.clear(), fin_off.clear(), fin_first.clear();
+                        fin_moff.assign(1, 0);
+                        for (size_t e = 0; e < st_i.size(); ++e) {
+                            if (e == 0 || st_i[e] != st_i[e - 1]) {
+                                const int j = lo_j[(size_t)st_i[e]];
+                                fin_ids.push_back(sel[j]);
+                                fin_off.push_back(set->out_off[(size_t)j]);
+                                fin_first.push_back((int)e);
+                                fin_moff.push_back(fin_moff.back());
+                            }
+                            ++fin_moff.back();
+                        }
+                        const int nf = (int)fin_ids.size();
+                        fin_res.resize((size_t)nf);
+                        select_run(R, stream, PairSel{nf, fin_ids.data()}, fin_off.data(), fin_moff.data(),
+                                   st_m.data(), nullptr, nullptr, fin_res.data(), nullptr, model_chunk, tile, false,
+                                   stm);
+                        for (int f = 0; f < nf; ++f) {
+                            const SelectResult &W = fin_res[(size_t)f];
+                            if (W.best_index < 0) continue;
+                            const size_t e = (size_t)fin_first[(size_t)f] + (size_t)W.best_index;
+                            const int j = lo_j[(size_t)st_i[e]];
+                            if (lo_step_offer(track[(size_t)j], strack[(size_t)j], results[j].best_candidate, st_r[e],
+                                              2 + Q, W.best_score, W.num_inliers))
+                                models[j] = st_m[e];
+                        }
                     }
                 }
             }
@@ -4363,9 +4745,68 @@ void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
         if (K.source != 0) Q.score_initial = Q.score_final = K.score;
         for (int t = 0; t < 3; ++t) Q.num_inliers[t] = K.counts[t];
         lo_info[j] = RansacLoInfo{K.lo_runs, K.lo_accepted, K.lo_index, 0};
+        if (steps_info) {
+            const LoStepTrack &S = strack[(size_t)j];
+            steps_info[j] = RansacLoStepsInfo{S.lo_step, S.lo_stage, S.offers, S.accepted};
+        }
+    }
+    // rounds = 0: the lists of an overall best that came from a step are the ones select
+    // returns for that single model (no stage of a step forms tight lists)
+    if (lo_steps > 0 && rounds == 0 && inlier_idx) {
+        std::vector<int32_t> one_ids;
+        std::vector<int> one_j;
+        std::vector<int64_t> one_off, one_moff(1, 0);
+        std::vector<Model> one_models;
+        for (int j = 0; j < num_sel; ++j) {
+            if (track[(size_t)j].source != kLoSourceStep) continue;
+            one_j.push_back(j);
+            one_ids.push_back(sel[j]);
+            one_off.push_back(set->out_off[(size_t)j]);
+            one_moff.push_back((int64_t)one_j.size());
+            one_models.push_back(models[j]);
+        }
+        if (!one_j.empty()) {
+            const int no = (int)one_j.size();
+            std::vector<SelectResult> one_res((size_t)no);
+            SelectTiming stm;
+            select_run(*set->R, stream, PairSel{no, one_ids.data()}, one_off.data(), one_moff.data(),
+                       one_models.data(), nullptr, nullptr, one_res.data(), inlier_idx, model_chunk, tile, false, stm);
+            for (int i = 0; i < no; ++i) {
+                const LoTrack &K = track[(size_t)one_j[(size_t)i]];
+                const SelectResult &W = one_res[(size_t)i];
+                if (W.best_index != 0 || W.best_score != K.score || W.num_inliers[0] != K.counts[0] ||
+                    W.num_inliers[1] != K.counts[1] || W.num_inliers[2] != K.counts[2])
+                    throw std::logic_error("ransac_lo_steps: a step's model scored differently");
+            }
+        }
     }
     // ---- refine: once, the overall bests ----
     refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
+}
+} // namespace
+
+void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
+                   int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
+                   int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
+                   int64_t model_chunk) {
+    ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
+                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, 0, nullptr);
+}
+
+void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                         uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
+                         Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
+                         RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
+                         int64_t model_chunk) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (lo_steps < 1 || lo_steps > kLoStepsMax) throw std::invalid_argument("lo_steps must be in 1..64");
+    if (num_sel > 0 && !steps_info) throw std::invalid_argument("null steps_info");
+    if (set->opts.num_lsq_iterations < 0 || set->opts.num_lsq_iterations > kLoStepLsqIterMax)
+        throw std::invalid_argument("num_lsq_iterations must be in 0..254 with lo_steps");
+    if (!(set->opts.threshold_multiplier > 0.0) || !(set->opts.threshold_multiplier <= DBL_MAX))
+        throw std::invalid_argument("threshold_multiplier must be positive and finite with lo_steps");
+    ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
+                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, lo_steps, steps_info);
 }
 
 void ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts, const int32_t *candidate,

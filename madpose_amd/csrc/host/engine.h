@@ -221,6 +221,38 @@ void pair_set_norm_scales(const PairSet *set, double *out);
 // are the tight ones
 void refine_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int rounds, Model *models,
                 RefineResult *results, int32_t *inlier_idx, bool relax = false);
+// lsq_fit_set (mp_lsq_fit_set): one least-squares fit per entry on a random subset of the
+// entry's inliers -- LeastSquaresFit (rule 0, include/mp_subset.h kSubsetLsq) or the non-minimal
+// fit of an LO step (rule 1, kSubsetNonmin) of the estimators' LocalOptimization.  Entry e is a
+// model (user units, in and out) of pair pair_ids[e] (null: e; a pair MAY repeat) with solver
+// type solver_types[e], threshold factor factors[e] and the subset streams streams[e] /
+// substreams[e].  Per entry: the model's score (score_models' bits) and tight counts, the wide
+// lists err < thr * factor and their lengths, the subset of include/mp_subset.h of them (size by
+// the rule) with its lengths; when the rule skips the entry or the subset fails
+// lm_refine_batch_device's size test, status 3 and the model's bytes kept; otherwise the device
+// LM (kind 0 for rule 0, 1 for rule 1) on the subset from the model, status 1: its result,
+// anything else: the input bytes.  subset_idx (nullable): refine's inlier_idx layout over the
+// entries.  The pairs' list buffers are not touched and nothing stays in the set.
+struct LsqFitResult {
+    double score;
+    int32_t num_inliers[3], num_wide[3], subset_sizes[3];
+    int32_t status; // 0..3 as lm_refine_batch_device
+};
+void lsq_fit_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, const int32_t *solver_types,
+                 const double *factors, int rule, uint64_t seed, const int32_t *streams, const int32_t *substreams,
+                 Model *models, LsqFitResult *results, int32_t *subset_idx, int64_t entry_chunk);
+// Test hooks.  subset_select_device (mp_debug_subset_select): lsq_subset_kernel on three given
+// strictly ascending lists (idx[offsets[t] .. offsets[t + 1]), offsets[0] = 0) with the size k;
+// the subset's lists to out_idx + offsets[t], their lengths to out_sizes.
+// subset_select_host_hook (mp_debug_subset_select_host): the header's host form, no device.
+// lsq_subset_size (mp_debug_lsq_subset_size): the size rule; returns 0 when it skips.
+void subset_select_device(const int64_t *offsets, const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                          int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx, int32_t *out_sizes,
+                          int device);
+void subset_select_host_hook(const int64_t *offsets, const int32_t *idx, int64_t k, uint64_t seed, int32_t pair,
+                             int32_t stream, int32_t substream, uint64_t key_mask, int32_t *out_idx,
+                             int32_t *out_sizes);
+int lsq_subset_size(int rule, int solver_type, int variant, int mu, int nu, const int32_t *sizes, int64_t *k);
 void select_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *model_offsets,
                 const Model *models, double *scores, int32_t *counts, SelectResult *results, int32_t *inlier_idx,
                 int64_t model_chunk);
@@ -300,6 +332,22 @@ void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
                    int64_t model_chunk);
+// ransac_lo_steps_set (mp_ransac_lo_steps_set): ransac_lo_set with the num_lo_steps steps of the
+// estimators' LocalOptimization after each local optimisation (host/ransac_lo_steps.h): lo_steps
+// steps per entry whose minimal best was replaced, from the model the relaxed refinement
+// returned; all steps of all such entries go through each stage in one lsq_fit_run (2 +
+// num_lsq_iterations runs and one select per checkpoint), every intermediate model is offered
+// to the overall best.  steps_info: one per entry.  With rounds = 0 the lists of an overall best
+// that a step produced are select's for that model.
+struct RansacLoStepsInfo {
+    int32_t lo_step, lo_stage;              // the step and stage that gave the overall best; -1: no step did
+    int32_t lo_step_offers, lo_step_accepted; // the steps' offers to the overall best; those accepted
+};
+void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
+                         uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
+                         Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
+                         RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
+                         int64_t model_chunk);
 // Test hook (mp_debug_ransac_lo_track; no device): host/ransac_lo_track.h walked over
 // num_rounds rounds in each of which the minimal best was replaced (its score and counts,
 // its candidate index, and its LO's rounds_accepted, score_final and counts).  score: the

@@ -145,6 +145,26 @@ struct RelaxedSweepOut {
     double score;
     int count[3], relaxed[3];
 };
+// One entry of mp_lsq_fit_set's launches (kernels/lsq_subset.h): a model of pair `pair` with
+// its own slice of the call's workspace, so a pair may occur in several entries of a launch.
+// The wide lists err < thr * factor go to ws + ws_off + t * stride (stride = the pair's n), the
+// subset's lists to ws + ws_off + (3 + t) * stride.  stype: the solver type the size rule reads;
+// rule: kSubsetLsq / kSubsetNonmin (include/mp_subset.h), or -1 for the given size k (the
+// subset test hook); stream / substream: the entry's in the subset's keys.
+struct LsqEntry {
+    int pair, stype, rule, k;
+    uint32_t stream, substream;
+    int stride, pad;
+    int64_t ws_off;
+    double factor;
+};
+// Its outcome.  lsq_sweep_kernel: the MSAC score (score_models_kernel's sum), the three tight
+// counts err < thr and the lengths of the three wide lists; lsq_subset_kernel: the size asked
+// for (k; -1: the rule skipped the entry) and the lengths of the subset's three lists.
+struct LsqOut {
+    double score;
+    int tight[3], wide[3], sub[3], k;
+};
 // One workgroup of select_score_kernel (kernels/select_batch.h; planned by
 // host/select_plan.h): `count` consecutive candidates of pair `pair` (of the run), their
 // records at rec .. rec + count - 1 of the slab on the device.

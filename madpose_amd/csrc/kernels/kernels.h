@@ -149,6 +149,20 @@ hipError_t launch_refine_sweep_relaxed(hipStream_t s, int variant, const PairDat
 hipError_t launch_lm_pairs(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs, const LmJob *jobs,
                            const LmPairRef *refs, int njobs, const int *idx, Model *out, int *status);
 
+// Least-squares fits on random inlier subsets (lsq_subset.h; mp_lsq_fit_set).  One workgroup
+// per entry; entry k's model record is recs[k], its outcome out[k], its workspace slice ws +
+// entries[k].ws_off (6 * stride ints: the three wide lists, then the three subset lists, each
+// `stride` = the pair's n apart).
+// launch_lsq_sweep: the score as launch_score_models gives it, the tight counts err < thr and
+// the wide ascending lists err < thr * entries[k].factor with their lengths.
+hipError_t launch_lsq_sweep(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                            const LsqEntry *entries, const ScoreRec *recs, int nentries, int *ws, LsqOut *out);
+// launch_lsq_subset: the subset (include/mp_subset.h) of the wide lists of lengths out[k].wide,
+// its size by the entry's rule (or entries[k].k for rule -1): out[k].k (-1: skipped by the rule)
+// and out[k].sub, the subset's list lengths.
+hipError_t launch_lsq_subset(hipStream_t s, const LsqEntry *entries, int nentries, int *ws, LsqOut *out, int variant,
+                             int mu, int nu, uint64_t seed, uint64_t key_mask);
+
 // Ranking of candidates over the resident pairs (select_batch.h; mp_select_batch).
 // Work item k = items[k].count (<= tile) candidates of pair items[k].pair with the records
 // recs[items[k].rec ..]; candidate j of the item has position at = base + items[k].rec + j
