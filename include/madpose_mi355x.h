@@ -415,6 +415,54 @@ int mp_pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, c
                        const double *d0, const double *d1, const double *min_depth, const double *cam0,
                        const double *cam1, const mp_ransac_options *options, const mp_estimator_config *config,
                        int device, mp_pair_set **out);
+/* mp_pair_set_create_device: mp_pair_set_create from arrays that are already on `device` --
+ * keypoints out of a matcher, depths out of a depth network.  The set is, bit for bit, the one
+ * mp_pair_set_create builds from the same numbers (the screening magnitudes of calibrated
+ * pairs to the last few bits; no result depends on them), so every stage returns the same
+ * bytes on it.  Host arguments (variant, num_pairs, offsets, min_depth, cam0, cam1, options,
+ * config, device) exactly as there.  Device arguments, in mp_device_pairs:
+ *   x0, x1          T x 2 interleaved pixel coordinates (T = offsets[num_pairs]) of element
+ *                   type xy_type: 0 float32 (every value widened to double exactly), 1 float64;
+ *   d0, d1          T depth priors of element type depth_type -- or
+ *   depth_maps      a HOST table of num_maps device pointers to contiguous row-major 2-D maps
+ *                   of one element type map_type, with map_dims (host, num_maps x 4: h, w,
+ *                   image_h, image_w as mp_get_depths takes them) and map_ids (host, num_pairs x
+ *                   2: the map of side 0 / side 1 of each pair; a map may serve many pairs and
+ *                   either side).  The prior of a correspondence is mp_get_depths' value for
+ *                   the pair's keypoint: keypoint * (w / image_w, h / image_h) in double, rint,
+ *                   clipped, [row, col].
+ *   Exactly one depth source: d0 / d1 null with the maps, the map fields null / 0 with d0 / d1.
+ *   producer_stream a hipStream_t (NULL: the device's null stream) on which the inputs are
+ *                   produced: the library records an event on it and makes its own stream wait
+ *                   for that event before the first read; the caller's stream is never
+ *                   synchronised with the host.
+ * The call returns after the library's own stream is synchronised; the inputs are not
+ * referenced after it returns and are never written.  MP_EINVAL, all before any launch or
+ * copy: everything mp_pair_set_create checks, type codes outside {0, 1}, both or neither
+ * depth source, map ids outside 0 .. num_maps - 1, non-positive map or image sizes, and for
+ * every device pointer: not device memory of `device` (hipPointerGetAttributes), not aligned
+ * to its element type, or the bytes the kernels read not inside the allocation's address range
+ * (hipMemGetAddressRange) -- the message names the argument.  The runtime knows allocations,
+ * not tensors: an array carved out of a caching allocator's block (a PyTorch tensor) is bounded
+ * by that BLOCK, so an array that is merely shorter than offsets[num_pairs] inside a larger block
+ * is NOT refused here -- the caller's shapes are the caller's to check (PairSet.from_device checks
+ * them).  The kernels assume element alignment only.  num_pairs == 0 gives a valid empty set without touching the device. */
+typedef struct mp_device_pairs {
+    const void *x0, *x1;
+    int32_t xy_type;
+    int32_t depth_type;
+    const void *d0, *d1;
+    const void *const *depth_maps;
+    const int64_t *map_dims;
+    const int32_t *map_ids;
+    int32_t num_maps;
+    int32_t map_type;
+    void *producer_stream;
+} mp_device_pairs;
+int mp_pair_set_create_device(int variant, int32_t num_pairs, const int64_t *offsets, const mp_device_pairs *inputs,
+                              const double *min_depth, const double *cam0, const double *cam1,
+                              const mp_ransac_options *options, const mp_estimator_config *config, int device,
+                              mp_pair_set **out);
 int mp_pair_set_destroy(mp_pair_set *set);
 int mp_pair_set_info(const mp_pair_set *set, int32_t *variant, int32_t *num_pairs, int64_t *correspondences,
                      int64_t *resident_bytes, int32_t *device);
@@ -704,6 +752,19 @@ int mp_debug_ransac_timing(double *out /* MP_RANSAC_TIMING_VALUES */);
  * calibrated and scale-only sets only). */
 int mp_debug_pair_set_prep(int mode);
 int mp_debug_pair_set_rows(const mp_pair_set *set, int32_t pair, double *out /* 12 n */);
+/* mp_debug_pair_set_record: the data-dependent fields of one pair's device record (copied back
+ * from the device) -- [0..2] thr, [3..5] w, [6] loss_scale, [7] tie_scale, [8] the
+ * normalization scale, [9..19] ea eap exi eb ebp exj ed0 ed1 ex0 ex1 eab2, then the margin
+ * constants [20..21] s2, [22..23] U, [24..25] c0, [26..27] c1, [28] tau2, [29] fixed.
+ * mp_debug_ingest_info: the trip lengths of mp_pair_set_create_device's kernels -- the
+ * workgroup size, the chunk length of the staged sum of the normalization scale, the
+ * correspondences of one work item.  mp_debug_device_extent: base address and size of the
+ * allocation of `device` that holds ptr, as the device pointers' range check sees it. */
+#define MP_PAIR_RECORD_VALUES 30
+#define MP_INGEST_INFO_VALUES 3
+int mp_debug_pair_set_record(const mp_pair_set *set, int32_t pair, double *out /* MP_PAIR_RECORD_VALUES */);
+int mp_debug_ingest_info(int32_t *out /* MP_INGEST_INFO_VALUES */);
+int mp_debug_device_extent(const void *ptr, int device, int64_t *out /* 2 */);
 
 /* bougnoux_focals (src/hybrid_pose_two_focal_estimator.cpp:11-32; numpy twin
  * madpose/utils.py:25-56 bougnoux_numpy with p1 = p2 = 0): squared focal lengths

@@ -30,6 +30,8 @@ HYPOTHESIZE_SLOTS = (10, 16, 4)
 # mp_draw_set: Philox blocks per sample at most, the largest point_share (MP_DRAW_*);
 # mp_debug_ransac_timing's values
 DRAW_BLOCKS, DRAW_POINT_SHARE_MAX, RANSAC_TIMING_VALUES = 16, 256, 18
+# mp_debug_pair_set_record's and mp_debug_ingest_info's values (MP_PAIR_RECORD_VALUES, MP_INGEST_INFO_VALUES)
+PAIR_RECORD_VALUES, INGEST_INFO_VALUES = 30, 3
 
 c_double_p = ctypes.POINTER(ctypes.c_double)
 c_int32_p = ctypes.POINTER(ctypes.c_int32)
@@ -71,6 +73,23 @@ class mp_estimator_config(ctypes.Structure):
         ("ceres_use_nonmonotonic_steps", ctypes.c_int32),
         ("ceres_num_threads", ctypes.c_int32),
         ("reserved", ctypes.c_int32),
+    ]
+
+
+class mp_device_pairs(ctypes.Structure):
+    _fields_ = [
+        ("x0", ctypes.c_void_p),
+        ("x1", ctypes.c_void_p),
+        ("xy_type", ctypes.c_int32),
+        ("depth_type", ctypes.c_int32),
+        ("d0", ctypes.c_void_p),
+        ("d1", ctypes.c_void_p),
+        ("depth_maps", ctypes.POINTER(ctypes.c_void_p)),
+        ("map_dims", ctypes.POINTER(ctypes.c_int64)),
+        ("map_ids", ctypes.POINTER(ctypes.c_int32)),
+        ("num_maps", ctypes.c_int32),
+        ("map_type", ctypes.c_int32),
+        ("producer_stream", ctypes.c_void_p),
     ]
 
 
@@ -218,6 +237,14 @@ EXPORTS = {
                                           c_double_p, c_double_p, c_double_p, c_double_p,
                                           ctypes.POINTER(mp_ransac_options), ctypes.POINTER(mp_estimator_config),
                                           ctypes.c_int, ctypes.POINTER(ctypes.c_void_p)]),
+    "mp_pair_set_create_device": (ctypes.c_int, [ctypes.c_int, ctypes.c_int32, c_int64_p,
+                                                 ctypes.POINTER(mp_device_pairs), c_double_p, c_double_p, c_double_p,
+                                                 ctypes.POINTER(mp_ransac_options),
+                                                 ctypes.POINTER(mp_estimator_config), ctypes.c_int,
+                                                 ctypes.POINTER(ctypes.c_void_p)]),
+    "mp_debug_pair_set_record": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_double_p]),
+    "mp_debug_ingest_info": (ctypes.c_int, [c_int32_p]),
+    "mp_debug_device_extent": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, c_int64_p]),
     "mp_pair_set_destroy": (ctypes.c_int, [ctypes.c_void_p]),
     "mp_pair_set_info": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, c_int32_p, c_int64_p, c_int64_p, c_int32_p]),
     "mp_pair_set_norm_scales": (ctypes.c_int, [ctypes.c_void_p, c_double_p]),

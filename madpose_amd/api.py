@@ -1098,6 +1098,41 @@ def hypothesize_batch(variant, pairs, samples, options, est_config=None, chunk=0
     return out, norm
 
 
+def _device_array(a, name, shape):
+    """(address, element-type code 0 float32 / 1 float64, shape) of a device array given through
+    __cuda_array_interface__, checked: C-contiguous, of the given shape (None: any 2-D shape
+    with positive sides).  ValueError otherwise; the object is only inspected."""
+    try:
+        cai = a.__cuda_array_interface__
+    except Exception as e:
+        raise ValueError(f"{name} must be a device array (an object with __cuda_array_interface__): {e}") from None
+    typestr = cai.get("typestr")
+    code = {"<f4": 0, "=f4": 0, "<f8": 1, "=f8": 1}.get(typestr)
+    if code is None:
+        raise ValueError(f"{name} must be float32 or float64, got {typestr!r}")
+    shp = tuple(int(s) for s in cai.get("shape", ()))
+    if shape is None:
+        if len(shp) != 2 or shp[0] <= 0 or shp[1] <= 0:
+            raise ValueError(f"{name} must be a 2-D (h, w) map with positive sides, got shape {shp}")
+    elif shp != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)} (offsets[-1] correspondences), got {shp}")
+    strides = cai.get("strides")
+    if strides is not None:
+        item, want = 4 if code == 0 else 8, []
+        for s in reversed(shp):
+            want.append(item)
+            item *= s
+        if any(s > 1 and st != w for s, st, w in zip(shp, strides, reversed(want))):
+            raise ValueError(f"{name} must be C-contiguous")
+    ptr = cai.get("data", (0, False))[0]
+    size = 1
+    for s in shp:
+        size *= s
+    if size > 0 and not ptr:
+        raise ValueError(f"{name} has no device address")
+    return (int(ptr) or None), code, shp
+
+
 class PairSet:
     """Pairs set up once and resident on the device (mp_pair_set_*): hypothesize, select
     and refine as methods on them.
@@ -1115,19 +1150,7 @@ class PairSet:
 
     def __init__(self, variant, pairs, options, est_config=None, device=None):
         self._h = None
-        if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL, L.SCALE_ONLY):
-            raise ValueError("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)")
-        if est_config is None:
-            est_config = EstimatorConfig()
-        self.variant = variant
-        self.device = _DEFAULT_DEVICE if device is None else int(device)
-        self._hyp_error = None  # why hypothesize is not available on this set
-        if variant == L.SCALE_ONLY:
-            self._hyp_error = "hypothesize does not support scale only (variant 3)"
-        elif not est_config.use_shift:
-            self._hyp_error = "hypothesize does not support use_shift = False"
-        elif getattr(options, "use_ours", False) or getattr(options, "use_4p4d", False):
-            self._hyp_error = "hypothesize does not support the alternate MD solvers (use_ours / use_4p4d)"
+        est_config = self._bind(variant, options, est_config, device)
         o = options._to_c()
         c = est_config._to_c()
         P = len(pairs)
@@ -1142,10 +1165,144 @@ class PairSet:
         L.check(L.lib().mp_pair_set_create(variant, P, offsets.ctypes.data_as(L.c_int64_p), dp(X0), dp(X1), dp(D0),
                                            dp(D1), dp(MD), dp(C0), dp(C1), ctypes.byref(o), ctypes.byref(c),
                                            self.device, ctypes.byref(h)))
+        self._opened(h, P)
+
+    def _bind(self, variant, options, est_config, device):
+        """what both ways of creating a set do first: the variant check, the device, and why
+        hypothesize may not be available on the set; returns the config to use"""
+        if variant not in (L.CALIBRATED, L.SHARED_FOCAL, L.TWO_FOCAL, L.SCALE_ONLY):
+            raise ValueError("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)")
+        if est_config is None:
+            est_config = EstimatorConfig()
+        self.variant = variant
+        self.device = _DEFAULT_DEVICE if device is None else int(device)
+        self._hyp_error = None  # why hypothesize is not available on this set
+        if variant == L.SCALE_ONLY:
+            self._hyp_error = "hypothesize does not support scale only (variant 3)"
+        elif not est_config.use_shift:
+            self._hyp_error = "hypothesize does not support use_shift = False"
+        elif getattr(options, "use_ours", False) or getattr(options, "use_4p4d", False):
+            self._hyp_error = "hypothesize does not support the alternate MD solvers (use_ours / use_4p4d)"
+        return est_config
+
+    def _opened(self, h, P):
+        """... and last: keep the handle and fetch the normalization scales"""
         self._h = h
         norm = np.ones(max(P, 1))
         L.check(L.lib().mp_pair_set_norm_scales(self._h, _dp(norm)))
         self._norm = norm[:P]
+
+    @classmethod
+    def from_device(cls, variant, x0, x1, offsets, cam0, cam1, options, est_config=None, depth0=None, depth1=None,
+                    depth_maps=None, map_ids=None, image_sizes=None, min_depth=None, stream=None, device=None):
+        """A PairSet from arrays that are already on the device (mp_pair_set_create_device): the
+        set PairSet(...) builds from the same numbers, bit for bit, without the trip through the
+        host.
+
+        Device inputs -- any object with __cuda_array_interface__ (torch tensors on a ROCm device
+        have it), float32 or float64, C-contiguous: x0, x1 of shape (T, 2), the pixel coordinates
+        of all pairs; and the depth priors, either depth0, depth1 of shape (T,), or depth_maps, a
+        sequence of (h, w) maps of one dtype, looked up at the keypoints as get_depths does, with
+        map_ids (P, 2): the map of side 0 / side 1 of each pair, and image_sizes (M, 2) = the
+        (height, width) of the image each map belongs to (default: the map's own shape).  Host
+        inputs: offsets (P + 1 ints, pair p = rows offsets[p] .. offsets[p + 1] - 1; T =
+        offsets[-1]), cam0 / cam1 ((P, 3, 3) intrinsics, or (P, 2) principal points for the focal
+        variants), min_depth ((P, 2), default zeros).  stream: the stream the inputs are produced
+        on -- None (the null stream), an integer handle or an object with .cuda_stream; the
+        library's stream waits for it on the device, the host does not.  The inputs are only read
+        and are not referenced after the call returns.  ValueError, before any library call, for a
+        wrong dtype, shape, contiguity or length, and for both depth sources or none."""
+        self = cls.__new__(cls)
+        self._h = None
+        est_config = self._bind(variant, options, est_config, device)
+        offs = np.asarray(offsets)
+        if offs.ndim != 1 or offs.shape[0] < 1 or offs.dtype.kind not in "iu":
+            raise ValueError("offsets must be a 1-D integer array of P + 1 values")
+        offs = np.ascontiguousarray(offs, dtype=np.int64)
+        P = offs.shape[0] - 1
+        if offs[0] != 0 or np.any(np.diff(offs) < 0):
+            raise ValueError("offsets must start at 0 and must not decrease")
+        T = int(offs[-1])
+        ncam = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
+
+        def host(a, shape, name):
+            a = np.ascontiguousarray(np.asarray(a, dtype=np.float64))
+            if a.size != P * shape or (a.ndim and a.shape[0] != P and P > 0):
+                raise ValueError(f"{name} must hold {shape} values for each of the {P} pairs")
+            return a.reshape(-1)
+        C0, C1 = host(cam0, ncam, "cam0"), host(cam1, ncam, "cam1")
+        MD = np.zeros(2 * P) if min_depth is None else host(min_depth, 2, "min_depth")
+        X0, xt, _ = _device_array(x0, "x0", (T, 2))
+        X1, xt1, _ = _device_array(x1, "x1", (T, 2))
+        if xt != xt1:
+            raise ValueError("x0 and x1 must have the same dtype")
+        arrays = depth0 is not None or depth1 is not None
+        maps = depth_maps is not None or map_ids is not None or image_sizes is not None
+        if arrays and maps:
+            raise ValueError("both depth sources given: pass depth0 / depth1 or depth_maps / map_ids, not both")
+        if not arrays and not maps:
+            raise ValueError("no depth source given: pass depth0 / depth1 or depth_maps / map_ids")
+        inp = L.mp_device_pairs()
+        inp.x0, inp.x1, inp.xy_type = X0, X1, xt
+        keep = []
+        if arrays:
+            if depth0 is None or depth1 is None:
+                raise ValueError("depth0 and depth1 must both be given")
+            D0, dt, _ = _device_array(depth0, "depth0", (T,))
+            D1, dt1, _ = _device_array(depth1, "depth1", (T,))
+            if dt != dt1:
+                raise ValueError("depth0 and depth1 must have the same dtype")
+            inp.d0, inp.d1, inp.depth_type = D0, D1, dt
+        else:
+            if depth_maps is None or map_ids is None:
+                raise ValueError("the map source needs depth_maps and map_ids")
+            M = len(depth_maps)
+            if M == 0:
+                raise ValueError("depth_maps is empty")
+            ptrs, shapes, mts = [], [], set()
+            for m, dm in enumerate(depth_maps):
+                ptr, mt, shp = _device_array(dm, f"depth_maps[{m}]", None)
+                ptrs.append(ptr)
+                shapes.append(shp)
+                mts.add(mt)
+            if len(mts) != 1:
+                raise ValueError("all depth maps must have one dtype")
+            ids = np.asarray(map_ids)
+            if ids.dtype.kind not in "iu" or ids.shape != (P, 2):
+                raise ValueError(f"map_ids must be an integer array of shape ({P}, 2)")
+            if ids.size and (ids.min() < 0 or ids.max() >= M):
+                raise ValueError(f"map_ids must lie in 0..{M - 1}")
+            ids = np.ascontiguousarray(ids, dtype=np.int32)
+            if image_sizes is None:
+                sizes = np.asarray(shapes, dtype=np.int64).reshape(M, 2)
+            else:
+                sizes = np.asarray(image_sizes)
+                if sizes.dtype.kind not in "iu" or sizes.shape != (M, 2):
+                    raise ValueError(f"image_sizes must be an integer array of shape ({M}, 2)")
+                if np.any(sizes <= 0):
+                    raise ValueError("image_sizes must be positive")
+            dims = np.ascontiguousarray(np.concatenate([np.asarray(shapes, dtype=np.int64).reshape(M, 2),
+                                                        sizes.astype(np.int64)], axis=1))
+            table = (ctypes.c_void_p * M)(*ptrs)
+            keep += [table, dims, ids]
+            inp.depth_maps = ctypes.cast(table, ctypes.POINTER(ctypes.c_void_p))
+            inp.map_dims = dims.ctypes.data_as(L.c_int64_p)
+            inp.map_ids = ids.ctypes.data_as(L.c_int32_p)
+            inp.num_maps, inp.map_type = M, mts.pop()
+        if stream is not None:
+            handle = getattr(stream, "cuda_stream", stream)
+            if isinstance(handle, bool) or not isinstance(handle, int) or handle < 0:
+                raise ValueError("stream must be None, an integer stream handle or an object with .cuda_stream")
+            inp.producer_stream = handle or None
+        o = options._to_c()
+        c = est_config._to_c()
+        self._sizes = [int(offs[p + 1] - offs[p]) for p in range(P)]
+        h = ctypes.c_void_p()
+        L.check(L.lib().mp_pair_set_create_device(variant, P, offs.ctypes.data_as(L.c_int64_p), ctypes.byref(inp),
+                                                  _dp(MD), _dp(C0), _dp(C1), ctypes.byref(o), ctypes.byref(c),
+                                                  self.device, ctypes.byref(h)))
+        self._opened(h, P)
+        return self
 
     # ---- lifetime ----
     def close(self):

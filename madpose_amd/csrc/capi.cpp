@@ -11,6 +11,7 @@
 #include "host/engine.h"
 #include "include/mp_subset.h"
 #include "host/hypothesis_plan.h"
+#include "host/ingest_plan.h"
 #include "host/pair_set_plan.h"
 #include "host/rng.h"
 #include "host/select_plan.h"
@@ -297,6 +298,39 @@ int mp_pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, c
     });
 }
 
+int mp_pair_set_create_device(int variant, int32_t num_pairs, const int64_t *offsets, const mp_device_pairs *inputs,
+                              const double *min_depth, const double *cam0, const double *cam1,
+                              const mp_ransac_options *options, const mp_estimator_config *config, int device,
+                              mp_pair_set **out) {
+    return guarded([&]() {
+        static_assert(mp::kPairRecordValues == MP_PAIR_RECORD_VALUES, "pair record constants");
+        if (!out) throw std::invalid_argument("null output");
+        *out = nullptr;
+        if (!options) throw std::invalid_argument("null options");
+        mp::DevicePairArrays in;
+        if (inputs) {
+            in.x0 = inputs->x0;
+            in.x1 = inputs->x1;
+            in.xy_type = inputs->xy_type;
+            in.d0 = inputs->d0;
+            in.d1 = inputs->d1;
+            in.depth_type = inputs->depth_type;
+            in.maps = inputs->depth_maps;
+            in.num_maps = inputs->num_maps;
+            in.map_type = inputs->map_type;
+            in.map_dims = inputs->map_dims;
+            in.map_ids = inputs->map_ids;
+            in.producer_stream = inputs->producer_stream;
+        } else if (num_pairs > 0) {
+            throw std::invalid_argument("null inputs");
+        }
+        *out = reinterpret_cast<mp_pair_set *>(mp::pair_set_create_device(variant, num_pairs, offsets, in, min_depth,
+                                                                          cam0, cam1, to_opts(options),
+                                                                          to_cfg(config), device));
+        return MP_OK;
+    });
+}
+
 int mp_pair_set_destroy(mp_pair_set *set) {
     return guarded([&]() {
         mp::pair_set_destroy(reinterpret_cast<mp::PairSet *>(set));
@@ -553,6 +587,27 @@ int mp_debug_pair_set_prep(int mode) {
 int mp_debug_pair_set_rows(const mp_pair_set *set, int32_t pair, double *out) {
     return guarded([&]() {
         mp::pair_set_rows(reinterpret_cast<const mp::PairSet *>(set), pair, out);
+        return MP_OK;
+    });
+}
+
+int mp_debug_pair_set_record(const mp_pair_set *set, int32_t pair, double *out) {
+    return guarded([&]() {
+        mp::pair_set_record(reinterpret_cast<const mp::PairSet *>(set), pair, out);
+        return MP_OK;
+    });
+}
+
+int mp_debug_ingest_info(int32_t *out) {
+    return guarded([&]() {
+        mp::ingest_info(out);
+        return MP_OK;
+    });
+}
+
+int mp_debug_device_extent(const void *ptr, int device, int64_t *out) {
+    return guarded([&]() {
+        mp::device_extent(ptr, device, out);
         return MP_OK;
     });
 }

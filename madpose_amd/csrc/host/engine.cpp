@@ -3733,6 +3733,104 @@ PairSet *pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets,
     return S.release();
 }
 
+PairSet *pair_set_create_device(int variant, int32_t num_pairs, const int64_t *offsets, const DevicePairArrays &in,
+                                const double *min_depth, const double *cam0, const double *cam1,
+                                const RansacOptions &opts, const EstimatorConfig &cfg, int device) {
+    if (variant < 0 || variant > 3)
+        throw std::invalid_argument("variant must be 0 (calibrated), 1 (shared focal), 2 (two focal) or 3 (scale only)");
+    if (num_pairs < 0) throw std::invalid_argument("negative pair count");
+    {
+        PairInput none; // (the option checks of every entry point)
+        validate(none, opts);
+    }
+    if (num_pairs > 0) {
+        if (!offsets || !min_depth || !cam0 || !cam1)
+            throw std::invalid_argument("null offsets, min_depth or cameras");
+        auto type_ok = [](int t) { return t == 0 || t == 1; };
+        if (!type_ok(in.xy_type)) throw std::invalid_argument("xy_type must be 0 (float32) or 1 (float64)");
+        if (offsets[0] < 0) throw std::invalid_argument("offsets must be non-negative");
+        for (int32_t p = 0; p < num_pairs; ++p) {
+            if (offsets[p + 1] < offsets[p]) throw std::invalid_argument("offsets must not decrease");
+            if (offsets[p + 1] - offsets[p] > kRefinePairMax) throw std::invalid_argument("pair too large");
+        }
+        if (offsets[num_pairs] - offsets[0] > kPairSetMaxCorr)
+            throw std::invalid_argument("more than 2^26 correspondences in one set");
+        const bool arrays = in.d0 || in.d1;
+        const bool maps = in.maps || in.num_maps != 0 || in.map_dims || in.map_ids;
+        if (arrays && maps)
+            throw std::invalid_argument("both depth sources given: pass d0 / d1 or the depth maps, not both");
+        if (!arrays && !maps)
+            throw std::invalid_argument("no depth source given: pass d0 / d1 or the depth maps");
+        if (arrays) {
+            if (!type_ok(in.depth_type)) throw std::invalid_argument("depth_type must be 0 (float32) or 1 (float64)");
+            if (offsets[num_pairs] > 0 && (!in.d0 || !in.d1)) throw std::invalid_argument("null input array d0 or d1");
+        } else {
+            if (!type_ok(in.map_type)) throw std::invalid_argument("map_type must be 0 (float32) or 1 (float64)");
+            if (in.num_maps <= 0 || !in.maps || !in.map_dims || !in.map_ids)
+                throw std::invalid_argument("the map source needs maps, map_dims, map_ids and num_maps > 0");
+            for (int32_t m = 0; m < in.num_maps; ++m) {
+                const int64_t *d = in.map_dims + 4 * (size_t)m;
+                if (d[0] <= 0 || d[1] <= 0 || d[2] <= 0 || d[3] <= 0)
+                    throw std::invalid_argument("map_dims[" + std::to_string(m) + "]: bad depth-map or image size");
+                if (!in.maps[m]) throw std::invalid_argument("depth_maps[" + std::to_string(m) + "] is null");
+            }
+            for (int64_t j = 0; j < 2 * (int64_t)num_pairs; ++j)
+                if (in.map_ids[j] < 0 || in.map_ids[j] >= in.num_maps)
+                    throw std::invalid_argument("map_ids[" + std::to_string(j) + "] = " + std::to_string(in.map_ids[j]) +
+                                                " is outside the " + std::to_string(in.num_maps) + " maps");
+        }
+        if (offsets[num_pairs] > 0 && (!in.x0 || !in.x1)) throw std::invalid_argument("null input array x0 or x1");
+    }
+    std::unique_ptr<PairSet> S(new PairSet());
+    S->device = device;
+    S->variant = variant;
+    S->opts = opts;
+    S->cfg = cfg;
+    S->num_pairs = num_pairs;
+    if (num_pairs > 0) {
+        CtxLease lease(device);
+        S->R.reset(new ResidentPairs(lease.c->stream, device, variant, num_pairs, offsets, in, min_depth, cam0, cam1, opts,
+                                     cfg));
+    }
+    std::lock_guard<std::mutex> lk(g_sets_mu);
+    g_sets.push_back(S.get());
+    return S.release();
+}
+
+void pair_set_record(const PairSet *set, int32_t pair, double *out) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (pair < 0 || pair >= set->num_pairs) throw std::invalid_argument("pair outside the set");
+    if (!out) throw std::invalid_argument("null output");
+    std::lock_guard<std::mutex> lk(const_cast<PairSet *>(set)->mu);
+    const ResidentPairs &R = *set->R;
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+    PairConst C;
+    MP_HIP(hipMemcpyAsync(&C, R.d_C.p + pair, sizeof(PairConst), hipMemcpyDeviceToHost, stream));
+    MP_HIP(hipStreamSynchronize(stream));
+    pair_record_values(C, R.norm_scale[(size_t)pair], out);
+}
+
+void ingest_info(int32_t *out) {
+    if (!out) throw std::invalid_argument("null output");
+    out[0] = kIngestBlock;
+    out[1] = kIngestChunk;
+    out[2] = kIngestSpan;
+}
+
+void device_extent(const void *ptr, int device, int64_t *out) {
+    if (!ptr || !out) throw std::invalid_argument("null pointer or output");
+    CtxLease lease(device);
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, const_cast<void *>(ptr)) != hipSuccess) {
+        (void)hipGetLastError();
+        throw std::invalid_argument("the pointer has no allocation range");
+    }
+    out[0] = (int64_t)(uintptr_t)base;
+    out[1] = (int64_t)size;
+}
+
 void pair_set_destroy(PairSet *set) {
     if (!set) return;
     {

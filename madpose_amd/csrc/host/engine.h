@@ -207,6 +207,35 @@ struct PairSet;
 PairSet *pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
                          const double *d0, const double *d1, const double *min_depth, const double *cam0,
                          const double *cam1, const RansacOptions &opts, const EstimatorConfig &cfg, int device);
+// pair_set_create from arrays that are already on `device` (mp_pair_set_create_device;
+// host/ingest_plan.h, kernels/ingest_pairs.h): the set is the one pair_set_create builds from
+// the same numbers, bit for bit.  x0, x1: T x 2 interleaved pixels of type xy_type (0 float32,
+// widened exactly, 1 float64).  The depth priors: d0, d1 (T values of depth_type), or num_maps
+// maps (host table `maps` of device pointers, h x w row-major of map_type; map_dims num_maps x 4
+// = h, w, image_h, image_w; map_ids num_pairs x 2 = the map of side 0 / 1 of each pair) looked
+// up at the pair's keypoints with get_depths' arithmetic -- exactly one of the two.  The set's
+// stream waits for an event recorded on producer_stream (a hipStream_t; null: the null stream)
+// before its first read; the call returns after its own stream is synchronised and the inputs
+// are neither written nor referenced afterwards.  std::invalid_argument before any launch or
+// copy: what pair_set_create refuses, type codes outside {0, 1}, both or neither depth source,
+// map ids outside the table, non-positive map or image sizes, and every device pointer that
+// is not device memory of `device`, not aligned to its element type, or whose allocation
+// (hipMemGetAddressRange) does not hold the bytes the kernels read.
+struct DevicePairArrays {
+    const void *x0 = nullptr, *x1 = nullptr;
+    int xy_type = 1;
+    const void *d0 = nullptr, *d1 = nullptr;
+    int depth_type = 1;
+    const void *const *maps = nullptr;
+    int32_t num_maps = 0;
+    int map_type = 0;
+    const int64_t *map_dims = nullptr;
+    const int32_t *map_ids = nullptr;
+    void *producer_stream = nullptr;
+};
+PairSet *pair_set_create_device(int variant, int32_t num_pairs, const int64_t *offsets, const DevicePairArrays &in,
+                                const double *min_depth, const double *cam0, const double *cam1,
+                                const RansacOptions &opts, const EstimatorConfig &cfg, int device);
 void pair_set_destroy(PairSet *set); // null: nothing
 // resident_bytes: the rows (96 bytes per correspondence) and the list buffers allocated so
 // far (12 bytes per correspondence each: none after creation or hypothesize_set, one after
@@ -380,6 +409,13 @@ RansacTiming ransac_timing_last();
 // previous mode.  pair_set_rows: rows 0 .. 11 of a pair (12 n doubles).
 int pair_set_prep_mode(int mode);
 void pair_set_rows(const PairSet *set, int32_t pair, double *out);
+// mp_debug_pair_set_record: the data-dependent fields of the pair's device PairConst (copied
+// back) and its normalization scale, host/ingest_plan.h pair_record_values' order.
+// ingest_info: kIngestBlock, kIngestChunk, kIngestSpan.  device_extent: base and size of the
+// allocation of `device` that holds ptr (hipMemGetAddressRange), as the ingest's checks see it.
+void pair_set_record(const PairSet *set, int32_t pair, double *out);
+void ingest_info(int32_t *out);
+void device_extent(const void *ptr, int device, int64_t *out);
 
 // Standalone solvers on the device (mp_solve_* / mp_relpose_5pt).
 // alt: 0 default MD solver, 1 use_ours, 2 use_4p4d (two-focal)

@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../host/ingest_plan.h"
 #include "../host/pair_set_plan.h"
 #include "../include/mp_draw.h"
 #include "../include/mp_types.h"
@@ -20,6 +21,15 @@ hipError_t launch_prep_pair(hipStream_t s, const PairConst &C, const PairData &D
 // with launch_prep_pair's bits.  Ds / Cs / items: device arrays.
 hipError_t launch_prep_pairs(hipStream_t s, const PairData *Ds, const PairConst *Cs, const PrepItem *items,
                              int nitems);
+
+// The device ingest (ingest_pairs.h; host/ingest_plan.h): rows 0 .. 5 of resident pairs from the
+// caller's device arrays A.  launch_ingest_scale (shared / two focal): scale[k] = pair k's
+// normalization scale, make_problem's bits (1 for an empty pair).  launch_ingest_rows: rows 0 .. 5
+// of the items' correspondences (Ds[k].x0u .. d1) and stats[item]; scale: launch_ingest_scale's
+// (not read for calibrated geometry).  Ps / Ds / items / scale / stats: device arrays.
+hipError_t launch_ingest_scale(hipStream_t s, const IngestArgs &A, const IngestPair *Ps, int np, double *scale);
+hipError_t launch_ingest_rows(hipStream_t s, const IngestArgs &A, const IngestItem *items, int nitems,
+                              const IngestPair *Ps, const PairData *Ds, const double *scale, IngestStats *stats);
 
 // MD minimal solver over the listed iterations (md_exact: R lanes per sample).
 hipError_t launch_md_solve(hipStream_t s, const PairData &D, const PairConst &C, const int *list, int nlist,

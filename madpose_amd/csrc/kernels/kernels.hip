@@ -1823,3 +1823,5 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 #include "hypothesize_batch.h"
 // the device sampler (mp_draw_set, mp_ransac_set)
 #include "draw_batch.h"
+// pair sets from arrays on the device (mp_pair_set_create_device)
+#include "ingest_pairs.h"
