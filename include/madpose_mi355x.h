@@ -733,6 +733,78 @@ int mp_ransac_lo_steps_set(mp_pair_set *set, int32_t num_sel, const int32_t *pai
                            int32_t *inlier_idx /* nullable */, int32_t *stopped /* num_sel, nullable */,
                            mp_ransac_lo_info *lo_info /* num_sel */, mp_ransac_lo_steps_info *steps_info /* num_sel */,
                            int64_t sample_chunk, int64_t model_chunk);
+/* Confidence-weighted sampling: mp_draw_set's and mp_ransac_*_set's samples drawn by a weight per
+ * correspondence (a matcher's confidence) instead of uniformly.  Every entry here is additive; the
+ * entries above and their bytes are unchanged.
+ *
+ * The rule, for a pair of n correspondences given weights w_i (float32 is widened exactly):
+ * valid weights are finite and 0 <= w_i <= 1; q_i = min(65535, floor(w_i * 65536)) as uint32 (a
+ * product with a power of two: exact); q_i = 0 masks correspondence i; c[0] = 0, c[i + 1] = c[i] +
+ * q_i in uint32, W = c[n]; n <= MP_DRAW_WEIGHT_MAX_N, so W < 2^32.  With k_max = k_pt if n >= k_pt
+ * else k_md, the pair is weighted iff #{q_i > 0} >= k_max; a pair given weights with fewer draws by
+ * mp_draw_set's uniform rule and is reported as not weighted.  For a weighted pair the type comes
+ * from word 0 as before; from word 1 on each word w proposes t = (uint64(w) * W) >> 32 and then the
+ * unique i with c[i] <= t < c[i + 1]; slot a takes the next proposal that differs from the slots
+ * before it; after MP_DRAW_BLOCKS blocks the open slots take the smallest unused indices with q_i >
+ * 0 in ascending order.  Counter, key and block order are mp_draw_set's, and the pair is still the
+ * pair's index in the set.  Integer-only, one function for host and device.  If all q_i are equal
+ * and positive the proposals are mp_draw_set's, so equal weights reproduce the uniform draw byte
+ * for byte.  The termination rule of the adaptive modes is unchanged: it reads the count ratios of
+ * the best model's lists, which under informative weights is conservative (it never stops earlier
+ * than it does without weights).
+ *
+ * mp_draw_weights_create: the tables of one set, built by one device launch.  weights: one value
+ * per correspondence of the set, concatenated in set order (dtype 0 float32, 1 float64), on the
+ * host (on_device 0) or on the set's device (on_device 1: checked as mp_pair_set_create_device
+ * checks its arrays; the build is ordered after producer_stream, a hipStream_t or NULL for the null
+ * stream, by an event, and the array is not read after the call returns).  given (nullable: every
+ * pair): num_pairs bytes, 0 = this pair draws uniformly and its rows of `weights` are ignored.
+ * MP_EINVAL: a null set or output, a dtype outside {0, 1}, a weight that is NaN, infinite, negative
+ * or above 1 (the message names the lowest such row of the set), a pair of more than
+ * MP_DRAW_WEIGHT_MAX_N correspondences given weights (pass given = 0 for it), and the sets
+ * mp_hypothesize_set refuses.  The handle belongs to its set, is immutable and lives outside the
+ * set: any number of calls may share it and a call still leaves nothing in the set that a later
+ * call can see.  mp_draw_weights_info: per pair, whether it is weighted (0 / 1), #{q_i > 0} and W
+ * (0 for the pairs not given weights); each output nullable.  mp_pair_set_destroy invalidates the
+ * set's handles (their device memory goes with the set): every later use of one is MP_EINVAL, and
+ * mp_draw_weights_destroy on it is still MP_OK.  mp_draw_weights_destroy(NULL) is MP_OK.
+ *
+ * mp_draw_weighted_set: mp_draw_set with the handle.  mp_ransac_weighted_set: one entry over
+ * mp_ransac_set's drawn mode (step 0; lo_rounds and lo_steps must be 0), mp_ransac_adaptive_set
+ * (step >= 1, lo_rounds 0), mp_ransac_lo_set (lo_rounds >= 1, lo_steps 0) and
+ * mp_ransac_lo_steps_set (lo_steps >= 1); stopped, lo_info and steps_info as the entry chosen
+ * takes them (unused ones may be NULL).  Each runs that entry's own checks and returns its
+ * MP_EINVALs, and its documented identities hold with the weighted draw in place of the uniform
+ * one.  MP_EINVAL also: a NULL handle, one of another set, one whose set was destroyed.
+ *
+ * mp_debug_draw_weights_host (no device): the table cum[0 .. n] and #{q_i > 0} of n weights, n <=
+ * MP_DRAW_WEIGHT_MAX_N.  mp_debug_draw_weighted_host (no device): one sample of a weighted pair
+ * from its table (MP_EINVAL if the table does not rise by 0 .. 65535 per entry from 0 or has fewer
+ * than k_max rises); out as mp_debug_draw_host's.  MP_DRAW_STAGE_ENTRIES: the device sampler reads
+ * a table of at most that many entries (n + 1) through LDS, larger ones from global memory. */
+#define MP_DRAW_WEIGHT_MAX_N 65535
+#define MP_DRAW_STAGE_ENTRIES 4096
+typedef struct mp_draw_weights mp_draw_weights;
+int mp_draw_weights_create(mp_pair_set *set, const void *weights, int32_t dtype, int32_t on_device,
+                           const uint8_t *given /* num_pairs, nullable */, void *producer_stream,
+                           mp_draw_weights **out);
+int mp_draw_weights_info(const mp_draw_weights *handle, int32_t *weighted /* num_pairs, nullable */,
+                         int32_t *positive /* num_pairs, nullable */, uint32_t *total /* num_pairs, nullable */);
+int mp_draw_weights_destroy(mp_draw_weights *handle);
+int mp_draw_weighted_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_sel, const int32_t *pair_ids,
+                         int32_t budget, uint64_t seed, int32_t point_share, int32_t *sample_types,
+                         int32_t *sample_idx, int32_t *sample_counts);
+int mp_ransac_weighted_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_sel, const int32_t *pair_ids,
+                           int32_t budget, int32_t step /* 0: fixed budget */, uint64_t seed, int32_t point_share,
+                           int32_t rounds, int32_t lo_rounds /* 0: none */, int32_t lo_steps /* 0: none */,
+                           mp_model *models /* num_sel */, mp_ransac_result *results /* num_sel */,
+                           int32_t *inlier_idx /* nullable */, int32_t *stopped /* num_sel, nullable */,
+                           mp_ransac_lo_info *lo_info, mp_ransac_lo_steps_info *steps_info, int64_t sample_chunk,
+                           int64_t model_chunk);
+int mp_debug_draw_weights_host(int64_t n, const void *weights, int32_t dtype, uint32_t *cum /* n + 1 */,
+                               int32_t *positive);
+int mp_debug_draw_weighted_host(int variant, int64_t n, const uint32_t *cum /* n + 1 */, uint64_t seed,
+                                int32_t point_share, int32_t pair, int32_t s, int32_t *out /* 10 */);
 /* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
  * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
  * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the

@@ -218,6 +218,9 @@ class mp_ransac_lo_steps_info(ctypes.Structure):
     ]
 
 
+# the weighted draw: the largest pair that may be given weights, the table entries (n + 1) the
+# device sampler reads through LDS (MP_DRAW_WEIGHT_MAX_N, MP_DRAW_STAGE_ENTRIES)
+DRAW_WEIGHT_MAX_N, DRAW_STAGE_ENTRIES = 65535, 4096
 LSQ_RULES = {"lsq": 0, "nonmin": 1}
 LO_STEPS_MAX = 64
 
@@ -295,6 +298,26 @@ EXPORTS = {
                                               ctypes.POINTER(mp_ransac_lo_info),
                                               ctypes.POINTER(mp_ransac_lo_steps_info), ctypes.c_int64,
                                               ctypes.c_int64]),
+    "mp_draw_weights_create": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.POINTER(ctypes.c_uint8), ctypes.c_void_p,
+                                              ctypes.POINTER(ctypes.c_void_p)]),
+    "mp_draw_weights_info": (ctypes.c_int, [ctypes.c_void_p, c_int32_p, c_int32_p, ctypes.POINTER(ctypes.c_uint32)]),
+    "mp_draw_weights_destroy": (ctypes.c_int, [ctypes.c_void_p]),
+    "mp_draw_weighted_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, c_int32_p,
+                                            ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, c_int32_p, c_int32_p,
+                                            c_int32_p]),
+    "mp_ransac_weighted_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, c_int32_p,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+                                              ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
+                                              c_int32_p, ctypes.POINTER(mp_ransac_lo_info),
+                                              ctypes.POINTER(mp_ransac_lo_steps_info), ctypes.c_int64,
+                                              ctypes.c_int64]),
+    "mp_debug_draw_weights_host": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
+                                                  ctypes.POINTER(ctypes.c_uint32), c_int32_p]),
+    "mp_debug_draw_weighted_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32),
+                                                   ctypes.c_uint64, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   c_int32_p]),
     "mp_debug_ransac_lo_track": (ctypes.c_int, [ctypes.c_int32, c_double_p, c_int32_p, c_int32_p, c_int32_p,
                                                 c_double_p, c_int32_p, c_double_p, c_int32_p]),
     "mp_debug_ransac_required": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_int32_p,

@@ -1544,16 +1544,110 @@ class PairSet:
             raise ValueError(f"at most 2^22 samples per call, got {ns} pairs x {budget}")
         return int(budget), int(seed), -1 if point_share is None else int(point_share)
 
-    def draw(self, budget, seed, point_share=None, pair_ids=None):
+    def draw_weights(self, weights, stream=None, given=None):
+        """Confidence weights for draw and ransac (mp_draw_weights_create): a DrawWeights, to be
+        passed as weights= to any number of calls on this set, and closed (or used as a context
+        manager) when done.
+
+        weights: a sequence with one entry per pair of the set -- a 1-D C-contiguous float32 or
+        float64 array of that pair's length, or None for a pair that draws uniformly -- or one
+        device array (an object with __cuda_array_interface__) of shape (T,) over the whole set,
+        float32 or float64; stream is then the stream it is produced on, as in from_device, and
+        given (optional, one bool per pair) marks the pairs whose rows count.  A weight is a
+        finite value in 0 .. 1 and is quantised to q = min(65535, floor(w * 65536)); q = 0 masks
+        the correspondence.  A sample's indices are then proposed with probability q_i / sum q
+        instead of uniformly; the sample types, the counter and the key are draw's, and equal
+        weights give draw's bytes.  A pair with fewer positive weights than its largest sample
+        draws uniformly (.weighted is False for it); a pair given weights may have at most
+        65535 correspondences.  The adaptive modes' termination rule still reads inlier count
+        ratios, which under informative weights is conservative.  ValueError, before any
+        library call, for a wrong length, dtype or contiguity and for a bad value in a host
+        array."""
+        h = self._live()
+        if self._hyp_error:
+            raise ValueError(self._hyp_error.replace("hypothesize", "draw_weights"))
+        P, T = len(self._sizes), int(sum(self._sizes))
+        producer = None
+        if hasattr(weights, "__cuda_array_interface__"):
+            ptr, code, _ = _device_array(weights, "weights", (T,))
+            if given is None:
+                mask = np.ones(P, dtype=np.uint8)
+            else:
+                mask = np.asarray(given)
+                if mask.shape != (P,) or mask.dtype.kind not in "biu":
+                    raise ValueError(f"given must hold one bool for each of the {P} pairs")
+                mask = np.ascontiguousarray(mask != 0, dtype=np.uint8)
+            if stream is not None:
+                handle = getattr(stream, "cuda_stream", stream)
+                if isinstance(handle, bool) or not isinstance(handle, int) or handle < 0:
+                    raise ValueError("stream must be None, an integer stream handle or an object with .cuda_stream")
+                producer = handle or None
+            on_device, keep = 1, weights
+        else:
+            if given is not None or stream is not None:
+                raise ValueError("given and stream go with a device array; a host sequence says None per pair")
+            try:
+                count = len(weights)
+            except TypeError:
+                raise ValueError("weights must be a sequence with one entry per pair, or a device array") from None
+            if count != P:
+                raise ValueError(f"one weights entry per pair of the set: {count} for {P} pairs")
+            arrays = []
+            for p, w in enumerate(weights):
+                if w is None:
+                    arrays.append(None)
+                    continue
+                a = np.asarray(w)
+                if a.dtype not in (np.float32, np.float64):
+                    raise ValueError(f"weights[{p}] must be float32 or float64, got {a.dtype}")
+                if a.ndim != 1 or a.shape[0] != self._sizes[p]:
+                    raise ValueError(f"weights[{p}] must be 1-D with the pair's {self._sizes[p]} values, "
+                                     f"got shape {a.shape}")
+                if not a.flags.c_contiguous:
+                    raise ValueError(f"weights[{p}] must be C-contiguous")
+                bad = np.flatnonzero(~((a >= 0) & (a <= 1)))
+                if bad.size:
+                    raise ValueError(f"weights[{p}][{int(bad[0])}] = {a[bad[0]]!r} is not a finite value in 0..1")
+                arrays.append(a)
+            all32 = all(a is None or a.dtype == np.float32 for a in arrays)
+            code = 0 if all32 else 1
+            keep = np.zeros(max(T, 1), dtype=np.float32 if all32 else np.float64)  # (float32 widens exactly)
+            mask = np.zeros(P, dtype=np.uint8)
+            at = 0
+            for p, a in enumerate(arrays):
+                if a is not None:
+                    keep[at:at + self._sizes[p]] = a
+                    mask[p] = 1
+                at += self._sizes[p]
+            ptr, on_device = keep.ctypes.data, 0
+        for p in range(P):
+            if mask[p] and self._sizes[p] > L.DRAW_WEIGHT_MAX_N:
+                raise ValueError(f"pair {p} has {self._sizes[p]} correspondences: a pair given weights may have "
+                                 f"at most {L.DRAW_WEIGHT_MAX_N} (pass None for it)")
+        wh = ctypes.c_void_p()
+        L.check(L.lib().mp_draw_weights_create(h, ptr, code, on_device,
+                                               mask.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)) if P else None,
+                                               producer, ctypes.byref(wh)))
+        del keep
+        return DrawWeights(self, wh, P)
+
+    def _weights_handle(self, weights):
+        if not isinstance(weights, DrawWeights):
+            raise ValueError("weights must be None or the object draw_weights returned")
+        return weights._live(self)
+
+    def draw(self, budget, seed, point_share=None, pair_ids=None, weights=None):
         """`budget` minimal samples per selected pair, drawn on the device (mp_draw_set): one
         (types, idx) per pair, the list hypothesize takes.  A pair too small for the MD solver
         gets none, one too small for the point solver only type 0.  The draw of a pair depends
         on seed, point_share (of 256: the share of point-solver samples; None: 128 hybrid, 256
         point solver only, 0 MD solver only, by the set's solver type) and the pair's index in
-        the set, not on the selection."""
+        the set, not on the selection.  weights (None, or draw_weights' object): the indices of
+        its weighted pairs are proposed by confidence (mp_draw_weighted_set)."""
         h = self._live()
         if self._hyp_error:
             raise ValueError(self._hyp_error.replace("hypothesize", "draw"))
+        wh = None if weights is None else self._weights_handle(weights)
         ids, ptr, sizes, _ = self._selection(pair_ids, len(self._sizes) if pair_ids is None else len(pair_ids), "entry")
         ns = len(sizes)
         budget, seed, share = self._check_draw(budget, seed, point_share, ns)
@@ -1562,8 +1656,12 @@ class PairSet:
         T = np.zeros(max(ns * budget, 1), dtype=np.int32)
         I = np.zeros(max(ns * budget, 1) * L.HYPOTHESIZE_SAMPLE_STRIDE, dtype=np.int32)
         C = np.zeros(ns, dtype=np.int32)
-        L.check(L.lib().mp_draw_set(h, ns, ptr, budget, seed, share, T.ctypes.data_as(L.c_int32_p),
-                                    I.ctypes.data_as(L.c_int32_p), C.ctypes.data_as(L.c_int32_p)))
+        if wh is not None:
+            L.check(L.lib().mp_draw_weighted_set(h, wh, ns, ptr, budget, seed, share, T.ctypes.data_as(L.c_int32_p),
+                                                 I.ctypes.data_as(L.c_int32_p), C.ctypes.data_as(L.c_int32_p)))
+        else:
+            L.check(L.lib().mp_draw_set(h, ns, ptr, budget, seed, share, T.ctypes.data_as(L.c_int32_p),
+                                        I.ctypes.data_as(L.c_int32_p), C.ctypes.data_as(L.c_int32_p)))
         offs = np.concatenate([[0], np.cumsum(C)])
         I = I.reshape(-1, L.HYPOTHESIZE_SAMPLE_STRIDE)
         return [(T[offs[j]:offs[j + 1]].copy(), I[offs[j]:offs[j + 1]].copy()) for j in range(ns)]
@@ -1599,7 +1697,7 @@ class PairSet:
                  slot[moffs[j]:moffs[j + 1]].copy()) for j in range(ns)]
 
     def ransac(self, budget=None, seed=0, point_share=None, samples=None, rounds=3, pair_ids=None, sample_chunk=0,
-               model_chunk=0, step=None, lo=None, lo_steps=None):
+               model_chunk=0, step=None, lo=None, lo_steps=None, weights=None):
         """Fixed-budget RANSAC on the selected pairs in one call (mp_ransac_set): draw ->
         hypothesize -> select -> refine on the device-resident pairs.  Exactly one of budget
         (samples drawn on the device as draw(budget, seed, point_share) draws them) and samples
@@ -1641,10 +1739,21 @@ class PairSet:
         checkpoint go through a stage in one launch sequence.  lo_step, lo_stage: the step and
         the stage that produced the overall best (-1: no step did; lo_stage is 2 +
         num_lsq_iterations for a step's last model); lo_step_offers, lo_step_accepted: the
-        offers made and those that became the overall best."""
+        offers made and those that became the overall best.
+
+        weights (None, or draw_weights' object; needs budget, refuses samples): the drawn samples
+        are draw(..., weights=weights)'s in every mode (mp_ransac_weighted_set), and each mode's
+        identity above holds with weights passed to both sides.  The termination rule is
+        unchanged: it reads inlier count ratios, so under informative weights it is conservative
+        and never stops a pair earlier than it does without weights."""
         h = self._live()
         if self._hyp_error:
             raise ValueError(self._hyp_error.replace("hypothesize", "ransac"))
+        wh = None
+        if weights is not None:
+            if samples is not None:
+                raise ValueError("weights go with a budget: given samples are not drawn")
+            wh = self._weights_handle(weights)
         if lo_steps is not None:
             if (isinstance(lo_steps, bool) or not isinstance(lo_steps, (int, np.integer))
                     or not 1 <= lo_steps <= L.LO_STEPS_MAX):
@@ -1695,7 +1804,18 @@ class PairSet:
         idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
         stopped = np.zeros(ns, dtype=np.int32)
         info = sinfo = None
-        if lo is not None and lo_steps is not None:
+        if wh is not None:
+            if lo is not None:
+                info = (L.mp_ransac_lo_info * ns)()
+            if lo_steps is not None:
+                sinfo = (L.mp_ransac_lo_steps_info * ns)()
+            L.check(L.lib().mp_ransac_weighted_set(h, wh, ns, ptr, budget, 0 if step is None else int(step), seed,
+                                                   share, int(rounds), 0 if lo is None else int(lo),
+                                                   0 if lo_steps is None else int(lo_steps), arr, res,
+                                                   idx.ctypes.data_as(L.c_int32_p),
+                                                   stopped.ctypes.data_as(L.c_int32_p), info, sinfo,
+                                                   int(sample_chunk), int(model_chunk)))
+        elif lo is not None and lo_steps is not None:
             info = (L.mp_ransac_lo_info * ns)()
             sinfo = (L.mp_ransac_lo_steps_info * ns)()
             L.check(L.lib().mp_ransac_lo_steps_set(h, ns, ptr, budget, int(step), seed, share, int(rounds), int(lo),
@@ -1741,6 +1861,53 @@ class PairSet:
             r.inlier_indices = [idx[base + t * n: base + t * n + q.num_inliers[t]].copy() for t in range(3)]
             out.append(r)
         return out
+
+
+class DrawWeights:
+    """The confidence weights of one PairSet (PairSet.draw_weights; mp_draw_weights_*): the
+    pairs' integer tables on the device, immutable, shared by any number of draw / ransac calls
+    on that set.  weighted (bool), positive (the number of correspondences with q > 0) and total
+    (the sum of the q) hold one entry per pair.  Use as a context manager, or close() (idempotent);
+    closing the PairSet first is fine.  A call with closed weights, or with the weights of another
+    set, raises ValueError."""
+
+    def __init__(self, pair_set, handle, num_pairs):
+        self._set, self._h = pair_set, handle
+        wt, pos = np.zeros(max(num_pairs, 1), dtype=np.int32), np.zeros(max(num_pairs, 1), dtype=np.int32)
+        tot = np.zeros(max(num_pairs, 1), dtype=np.uint32)
+        L.check(L.lib().mp_draw_weights_info(handle, wt.ctypes.data_as(L.c_int32_p), pos.ctypes.data_as(L.c_int32_p),
+                                             tot.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32))))
+        self.weighted = wt[:num_pairs] != 0
+        self.positive = pos[:num_pairs].copy()
+        self.total = tot[:num_pairs].astype(np.int64)
+
+    def close(self):
+        """Release the tables; idempotent."""
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None:
+            L.check(L.lib().mp_draw_weights_destroy(h))
+
+    def __enter__(self):
+        if self._h is None:
+            raise ValueError("the DrawWeights is closed")
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:  # (interpreter teardown)
+            pass
+
+    def _live(self, pair_set):
+        if getattr(self, "_h", None) is None:
+            raise ValueError("the DrawWeights is closed")
+        if pair_set is not self._set:
+            raise ValueError("the weights belong to another PairSet")
+        return self._h
 
 
 class LsqFitResult:

@@ -536,6 +536,93 @@ int mp_ransac_lo_steps_set(mp_pair_set *set, int32_t num_sel, const int32_t *pai
     });
 }
 
+int mp_draw_weights_create(mp_pair_set *set, const void *weights, int32_t dtype, int32_t on_device,
+                           const uint8_t *given, void *producer_stream, mp_draw_weights **out) {
+    return guarded([&]() {
+        static_assert(mp::kDrawWeightMaxN == MP_DRAW_WEIGHT_MAX_N && mp::kDrawStageEntries == MP_DRAW_STAGE_ENTRIES,
+                      "weighted draw constants");
+        if (!out) throw std::invalid_argument("null output handle");
+        *out = nullptr;
+        *out = reinterpret_cast<mp_draw_weights *>(mp::draw_weights_create(
+            reinterpret_cast<mp::PairSet *>(set), weights, dtype, on_device != 0, given, producer_stream));
+        return MP_OK;
+    });
+}
+
+int mp_draw_weights_info(const mp_draw_weights *handle, int32_t *weighted, int32_t *positive, uint32_t *total) {
+    return guarded([&]() {
+        mp::draw_weights_info(reinterpret_cast<const mp::DrawWeights *>(handle), weighted, positive, total);
+        return MP_OK;
+    });
+}
+
+int mp_draw_weights_destroy(mp_draw_weights *handle) {
+    return guarded([&]() {
+        mp::draw_weights_destroy(reinterpret_cast<mp::DrawWeights *>(handle));
+        return MP_OK;
+    });
+}
+
+int mp_draw_weighted_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_sel, const int32_t *pair_ids,
+                         int32_t budget, uint64_t seed, int32_t point_share, int32_t *sample_types,
+                         int32_t *sample_idx, int32_t *sample_counts) {
+    return guarded([&]() {
+        if (!set) throw std::invalid_argument("null pair set");
+        if (!handle) throw std::invalid_argument("null draw weights");
+        mp::draw_set(reinterpret_cast<mp::PairSet *>(set), num_sel, pair_ids, budget, seed, point_share, sample_types,
+                     sample_idx, sample_counts, reinterpret_cast<const mp::DrawWeights *>(handle));
+        return MP_OK;
+    });
+}
+
+int mp_ransac_weighted_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_sel, const int32_t *pair_ids,
+                           int32_t budget, int32_t step, uint64_t seed, int32_t point_share, int32_t rounds,
+                           int32_t lo_rounds, int32_t lo_steps, mp_model *models, mp_ransac_result *results,
+                           int32_t *inlier_idx, int32_t *stopped, mp_ransac_lo_info *lo_info,
+                           mp_ransac_lo_steps_info *steps_info, int64_t sample_chunk, int64_t model_chunk) {
+    return guarded([&]() {
+        if (!set) throw std::invalid_argument("null pair set");
+        if (!handle) throw std::invalid_argument("null draw weights");
+        mp::PairSet *S = reinterpret_cast<mp::PairSet *>(set);
+        const mp::DrawWeights *W = reinterpret_cast<const mp::DrawWeights *>(handle);
+        mp::Model *M = reinterpret_cast<mp::Model *>(models);
+        mp::RansacResult *Q = reinterpret_cast<mp::RansacResult *>(results);
+        mp::RansacLoInfo *LI = reinterpret_cast<mp::RansacLoInfo *>(lo_info);
+        if (step == 0 && (lo_rounds != 0 || lo_steps != 0))
+            throw std::invalid_argument("lo_rounds and lo_steps need step: they run inside the adaptive rounds");
+        if (lo_rounds == 0 && lo_steps != 0) throw std::invalid_argument("lo_steps needs lo_rounds");
+        if (step == 0)
+            mp::ransac_set(S, num_sel, pair_ids, budget, seed, point_share, nullptr, nullptr, nullptr, rounds, M, Q,
+                           inlier_idx, sample_chunk, model_chunk, W);
+        else if (lo_rounds == 0)
+            mp::ransac_adaptive_set(S, num_sel, pair_ids, budget, step, seed, point_share, rounds, M, Q, inlier_idx,
+                                    stopped, sample_chunk, model_chunk, W);
+        else if (lo_steps == 0)
+            mp::ransac_lo_set(S, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, M, Q, inlier_idx,
+                              stopped, LI, sample_chunk, model_chunk, W);
+        else
+            mp::ransac_lo_steps_set(S, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, lo_steps, M,
+                                    Q, inlier_idx, stopped, LI, reinterpret_cast<mp::RansacLoStepsInfo *>(steps_info),
+                                    sample_chunk, model_chunk, W);
+        return MP_OK;
+    });
+}
+
+int mp_debug_draw_weights_host(int64_t n, const void *weights, int32_t dtype, uint32_t *cum, int32_t *positive) {
+    return guarded([&]() {
+        mp::draw_weights_host(n, weights, dtype, cum, positive);
+        return MP_OK;
+    });
+}
+
+int mp_debug_draw_weighted_host(int variant, int64_t n, const uint32_t *cum, uint64_t seed, int32_t point_share,
+                                int32_t pair, int32_t s, int32_t *out) {
+    return guarded([&]() {
+        mp::draw_weighted_host(variant, n, cum, seed, point_share, pair, s, out);
+        return MP_OK;
+    });
+}
+
 int mp_debug_ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts,
                              const int32_t *candidate, const int32_t *lo_rounds_accepted, const double *lo_score,
                              const int32_t *lo_counts, double *score, int32_t *out) {

@@ -27,6 +27,7 @@
 
 #include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -42,6 +43,7 @@
 #include <string>
 #include <thread>
 
+#include "../include/mp_draw_weights.h"
 #include "../include/mp_score.h"
 #include "../kernels/kernels.h"
 #include "batch_draw.h"
@@ -580,6 +582,9 @@ struct PoolReaper {
 // exits with a set open exits cleanly.
 std::mutex g_sets_mu;
 std::vector<PairSet *> g_sets;
+// the live confidence-weight handles (mp_draw_weights_create .. destroy), of every set
+std::mutex g_weights_mu;
+std::vector<DrawWeights *> g_weights;
 void release_live_sets();
 struct SetReaper {
     ~SetReaper() { release_live_sets(); }
@@ -3395,6 +3400,11 @@ struct HypDraw {
     // per entry of the selection, nullable: the entry's samples are first[j], first[j] + 1, ...
     // of its pair (a later round of ransac_adaptive_set); sample_types are those samples'
     const int32_t *first = nullptr;
+    // the confidence weights of the call (DrawWeights; null: the uniform draw): the tables, the
+    // table offset of every pair of the set, and whether the pair draws by its table
+    const uint32_t *d_cum = nullptr;
+    const int64_t *d_cum_off = nullptr;
+    const unsigned char *d_weighted = nullptr;
 };
 // The compact output mode of hypothesize_run (mp_candidates_set, mp_ransac_set): instead of
 // the slot array, only the models that exist come back -- models in (sample, slot) order, in
@@ -3407,6 +3417,8 @@ struct HypCompact {
     int64_t bytes_slots = 0; // what the slot array and the counts would have been
 };
 
+constexpr bool kDrawStageDefault = true; // (the staged form against the global one)
+
 // One slab of device-drawn samples: items of the selection's entries over slab `s`, mapped to
 // the set's pairs, drawn into d_samples / d_types (slab positions).
 void draw_slab(hipStream_t stream, int v, const PairSel sel, const int64_t *soff, const HypSlab &s, const HypDraw &dr,
@@ -3416,6 +3428,14 @@ void draw_slab(hipStream_t stream, int v, const PairSel sel, const int64_t *soff
     for (DrawItem &it : h_items) it.pair = sel[it.pair];
     if (h_items.empty()) return;
     MP_HIP(hipMemcpyAsync(d_items, h_items.data(), sizeof(DrawItem) * h_items.size(), hipMemcpyHostToDevice, stream));
+    if (dr.d_cum) {
+        // (MADPOSE_DRAW_STAGE=0: every table from global memory, the A/B of tools/draw_weighted_bench.py)
+        const bool stage = env_flag("MADPOSE_DRAW_STAGE", kDrawStageDefault);
+        MP_HIP(launch_draw_samples_weighted(stream, v, d_items, (int)h_items.size(), dr.d_pair_n, dr.d_cum,
+                                            dr.d_cum_off, dr.d_weighted, stage, dr.seed, dr.point_share, d_samples,
+                                            d_types));
+        return;
+    }
     MP_HIP(launch_draw_samples(stream, v, d_items, (int)h_items.size(), dr.d_pair_n, dr.seed, dr.point_share,
                                d_samples, d_types));
 }
@@ -3683,8 +3703,50 @@ struct PairSet {
     }
 };
 
+// The confidence weights of one set (mp_draw_weights_*; include/mp_draw.h, kernels/
+// draw_weighted.h): the pairs' tables on the device and what mp_draw_weights_info returns.
+// Immutable once created; the calls that take it only read it, so the set holds nothing of it.
+// When its set is destroyed the device arrays go and `set` becomes null: the handle stays a
+// valid object that every call refuses until mp_draw_weights_destroy deletes it.
+struct DrawWeights {
+    const PairSet *set = nullptr;
+    std::unique_ptr<DevArray<uint32_t>> d_cum;          // T + num_pairs entries: pair p's at off[p] + p
+    std::unique_ptr<DevArray<int64_t>> d_cum_off;       // num_pairs
+    std::unique_ptr<DevArray<unsigned char>> d_weighted; // num_pairs
+    std::vector<int32_t> weighted, positive;
+    std::vector<uint32_t> total;
+};
+
 namespace {
+// the handles of `set` (null: of every set) lose their device arrays and their set
+void invalidate_weights(const PairSet *set) {
+    std::lock_guard<std::mutex> lk(g_weights_mu);
+    for (DrawWeights *w : g_weights) {
+        if (set && w->set != set) continue;
+        w->d_cum.reset();
+        w->d_cum_off.reset();
+        w->d_weighted.reset();
+        w->set = nullptr;
+    }
+}
+// a call's weights, checked under the set's lock: a live handle of this set
+void check_draw_weights(const PairSet *set, const DrawWeights *w) {
+    if (!w) throw std::invalid_argument("null draw weights");
+    std::lock_guard<std::mutex> lk(g_weights_mu);
+    if (std::find(g_weights.begin(), g_weights.end(), w) == g_weights.end())
+        throw std::invalid_argument("not a live draw-weights handle");
+    if (!w->set) throw std::invalid_argument("the draw weights' pair set was destroyed");
+    if (w->set != set) throw std::invalid_argument("the draw weights belong to another pair set");
+}
+void bind_weights(HypDraw &dr, const DrawWeights *w) {
+    if (!w || !w->d_cum) return; // (no pair was given weights: the uniform launch)
+    dr.d_cum = w->d_cum->p;
+    dr.d_cum_off = w->d_cum_off->p;
+    dr.d_weighted = w->d_weighted->p;
+}
+
 void release_live_sets() {
+    invalidate_weights(nullptr);
     std::vector<PairSet *> sets;
     {
         std::lock_guard<std::mutex> lk(g_sets_mu);
@@ -3840,7 +3902,165 @@ void pair_set_destroy(PairSet *set) {
         g_sets.erase(it);
     }
     { std::lock_guard<std::mutex> lk(set->mu); } // (a call still running on it ends first)
+    invalidate_weights(set);
     delete set;
+}
+
+DrawWeights *draw_weights_create(PairSet *set, const void *weights, int dtype, bool on_device,
+                                 const unsigned char *given, void *producer_stream) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (dtype != 0 && dtype != 1) throw std::invalid_argument("dtype must be 0 (float32) or 1 (float64)");
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_hyp_supported(set->variant, set->opts, set->cfg);
+    const int32_t np = set->num_pairs;
+    std::unique_ptr<DrawWeights> H(new DrawWeights());
+    H->set = set;
+    H->weighted.assign((size_t)np, 0);
+    H->positive.assign((size_t)np, 0);
+    H->total.assign((size_t)np, 0);
+    bool any = false;
+    for (int32_t p = 0; p < np; ++p) {
+        if (given && !given[p]) continue;
+        if (set->R->n[(size_t)p] > kDrawWeightMaxN)
+            throw std::invalid_argument("pair " + std::to_string(p) + " has more than 65535 correspondences: pass no weights for it");
+        any = any || set->R->n[(size_t)p] > 0;
+    }
+    if (any) {
+        if (!weights) throw std::invalid_argument("null weights");
+        const ResidentPairs &R = *set->R;
+        const int v = R.v, kmd = draw_k_md(v), kpt = draw_k_pt(v);
+        const int64_t T = R.T, e = dtype ? 8 : 4;
+        CtxLease lease(set->device);
+        hipStream_t stream = lease.c->stream;
+        const void *d_w = weights;
+        std::unique_ptr<DevArray<unsigned char>> up;
+        struct Event {
+            hipEvent_t ev = nullptr;
+            ~Event() {
+                if (ev) (void)hipEventDestroy(ev);
+            }
+        } produced;
+        if (on_device) {
+            // the pointer before any launch or copy, then the producer's work: an event on its
+            // stream, no host wait (as the device ingest)
+            check_device_array("weights", weights, ingest_bytes(T, 1, e), e, set->device);
+            MP_HIP(hipEventCreateWithFlags(&produced.ev, hipEventDisableTiming));
+            MP_HIP(hipEventRecord(produced.ev, static_cast<hipStream_t>(producer_stream)));
+            MP_HIP(hipStreamWaitEvent(stream, produced.ev, 0));
+        } else {
+            up.reset(new DevArray<unsigned char>((size_t)(T * e)));
+            MP_HIP(hipMemcpyAsync(up->p, weights, (size_t)(T * e), hipMemcpyHostToDevice, stream));
+            d_w = up->p;
+        }
+        H->d_cum.reset(new DevArray<uint32_t>((size_t)T + (size_t)np));
+        H->d_cum_off.reset(new DevArray<int64_t>((size_t)np));
+        H->d_weighted.reset(new DevArray<unsigned char>((size_t)np));
+        DevArray<int64_t> d_off((size_t)np);
+        DevArray<unsigned char> d_given((size_t)np);
+        DevArray<int> d_pos((size_t)np), d_bad(1);
+        DevArray<uint32_t> d_total((size_t)np);
+        std::vector<int64_t> cum_off((size_t)np);
+        for (int32_t p = 0; p < np; ++p) cum_off[(size_t)p] = R.off[(size_t)p] + p;
+        int bad = INT_MAX;
+        const int *d_n = set->pair_sizes(stream);
+        MP_HIP(hipMemcpyAsync(d_off.p, R.off.data(), sizeof(int64_t) * (size_t)np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(H->d_cum_off->p, cum_off.data(), sizeof(int64_t) * (size_t)np, hipMemcpyHostToDevice,
+                              stream));
+        if (given) MP_HIP(hipMemcpyAsync(d_given.p, given, (size_t)np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_bad.p, &bad, sizeof(int), hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemsetAsync(d_pos.p, 0, sizeof(int) * (size_t)np, stream));
+        MP_HIP(hipMemsetAsync(d_total.p, 0, sizeof(uint32_t) * (size_t)np, stream));
+        MP_HIP(launch_draw_weights_table(stream, d_w, dtype, d_off.p, d_n, given ? d_given.p : nullptr, np,
+                                         H->d_cum->p, d_pos.p, d_total.p, d_bad.p));
+        int bad_back = INT_MAX;
+        MP_HIP(hipMemcpyAsync(H->positive.data(), d_pos.p, sizeof(int) * (size_t)np, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipMemcpyAsync(H->total.data(), d_total.p, sizeof(uint32_t) * (size_t)np, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipMemcpyAsync(&bad_back, d_bad.p, sizeof(int), hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream)); // (the caller's array is not read after this)
+        if (bad_back != INT_MAX) {
+            const int p = (int)(std::upper_bound(R.off.begin(), R.off.end(), (int64_t)bad_back) - R.off.begin()) - 1;
+            throw std::invalid_argument("weights[" + std::to_string(bad_back) + "] (pair " + std::to_string(p) +
+                                        ", correspondence " + std::to_string(bad_back - R.off[(size_t)p]) +
+                                        ") is not a finite value in 0..1");
+        }
+        std::vector<unsigned char> flags((size_t)np, 0);
+        for (int32_t p = 0; p < np; ++p) {
+            const bool g = !given || given[p];
+            flags[(size_t)p] = g && H->positive[(size_t)p] >= draw_weighted_need(R.n[(size_t)p], kmd, kpt) ? 1 : 0;
+            H->weighted[(size_t)p] = flags[(size_t)p];
+        }
+        MP_HIP(hipMemcpyAsync(H->d_weighted->p, flags.data(), (size_t)np, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipStreamSynchronize(stream));
+    }
+    std::lock_guard<std::mutex> lk2(g_weights_mu);
+    g_weights.push_back(H.get());
+    return H.release();
+}
+
+void draw_weights_info(const DrawWeights *w, int32_t *weighted, int32_t *positive, uint32_t *total) {
+    if (!w) throw std::invalid_argument("null draw weights");
+    std::lock_guard<std::mutex> lk(g_weights_mu);
+    if (std::find(g_weights.begin(), g_weights.end(), w) == g_weights.end())
+        throw std::invalid_argument("not a live draw-weights handle");
+    if (!w->set) throw std::invalid_argument("the draw weights' pair set was destroyed");
+    if (weighted) std::copy(w->weighted.begin(), w->weighted.end(), weighted);
+    if (positive) std::copy(w->positive.begin(), w->positive.end(), positive);
+    if (total) std::copy(w->total.begin(), w->total.end(), total);
+}
+
+void draw_weights_destroy(DrawWeights *w) {
+    if (!w) return;
+    const PairSet *set = nullptr;
+    {
+        std::lock_guard<std::mutex> lk(g_weights_mu);
+        auto it = std::find(g_weights.begin(), g_weights.end(), w);
+        if (it == g_weights.end()) throw std::invalid_argument("not a live draw-weights handle");
+        g_weights.erase(it);
+        set = w->set;
+    }
+    // (a call still reading it ends first)
+    if (set) { std::lock_guard<std::mutex> lk(const_cast<PairSet *>(set)->mu); }
+    delete w;
+}
+
+void draw_weights_host(int64_t n, const void *weights, int dtype, uint32_t *cum, int32_t *positive) {
+    if (n < 0 || n > kDrawWeightMaxN) throw std::invalid_argument("n must be in 0..65535");
+    if (dtype != 0 && dtype != 1) throw std::invalid_argument("dtype must be 0 (float32) or 1 (float64)");
+    if (!cum || !positive || (n > 0 && !weights)) throw std::invalid_argument("null weights or output");
+    cum[0] = 0;
+    int32_t pos = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        const double w = dtype ? static_cast<const double *>(weights)[i] : (double)static_cast<const float *>(weights)[i];
+        uint32_t q;
+        if (!draw_quantise(w, &q))
+            throw std::invalid_argument("weights[" + std::to_string(i) + "] is not a finite value in 0..1");
+        cum[i + 1] = cum[i] + q;
+        pos += q > 0 ? 1 : 0;
+    }
+    *positive = pos;
+}
+
+void draw_weighted_host(int variant, int64_t n, const uint32_t *cum, uint64_t seed, int32_t point_share, int32_t pair,
+                        int32_t s, int32_t *out) {
+    if (variant < 0 || variant > 2) throw std::invalid_argument("variant must be 0, 1 or 2");
+    if (n < 0 || n > kDrawWeightMaxN) throw std::invalid_argument("n must be in 0..65535");
+    if (point_share < 0 || point_share > kDrawShareMax) throw std::invalid_argument("point_share must be in 0..256");
+    if (pair < 0 || s < 0 || !out || !cum) throw std::invalid_argument("negative pair or sample, or null table or output");
+    if (cum[0] != 0) throw std::invalid_argument("cum[0] must be 0");
+    int64_t pos = 0;
+    for (int64_t i = 0; i < n; ++i) {
+        if (cum[i + 1] < cum[i] || cum[i + 1] - cum[i] > kDrawWeightQMax)
+            throw std::invalid_argument("cum must rise by at most 65535 per entry");
+        pos += cum[i + 1] != cum[i] ? 1 : 0;
+    }
+    const int kmd = draw_k_md(variant), kpt = draw_k_pt(variant);
+    if (pos < draw_weighted_need(n, kmd, kpt))
+        throw std::invalid_argument("not a weighted pair: fewer positive weights than the largest sample");
+    int idx[8];
+    bool fill = false;
+    out[0] = draw_sample_weighted((int)n, kmd, kpt, seed, point_share, (uint32_t)pair, (uint32_t)s, cum, idx, &fill);
+    for (int a = 0; a < 8; ++a) out[1 + a] = idx[a];
+    out[9] = fill ? 1 : 0;
 }
 
 void pair_set_info(const PairSet *set, int32_t *variant, int32_t *num_pairs, int64_t *correspondences,
@@ -4181,10 +4401,12 @@ RansacTiming ransac_timing_last() {
 }
 
 void draw_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
-              int32_t point_share, int32_t *sample_types, int32_t *sample_idx, int32_t *sample_counts) {
+              int32_t point_share, int32_t *sample_types, int32_t *sample_idx, int32_t *sample_counts,
+              const DrawWeights *weights) {
     if (!set) throw std::invalid_argument("null pair set");
     check_draw_args(num_sel, budget, point_share);
     std::lock_guard<std::mutex> lk(set->mu);
+    if (weights) check_draw_weights(set, weights);
     check_hyp_supported(set->variant, set->opts, set->cfg);
     if (set->num_pairs == 0) {
         std::vector<char> seen;
@@ -4205,7 +4427,8 @@ void draw_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t bu
     if (S == 0) return;
     CtxLease lease(set->device);
     hipStream_t stream = lease.c->stream;
-    const HypDraw dr{seed, share, set->pair_sizes(stream)};
+    HypDraw dr{seed, share, set->pair_sizes(stream)};
+    bind_weights(dr, weights);
     const std::vector<HypSlab> slabs = hyp_slabs(S, 0);
     const size_t cap = (size_t)(slabs[0].s1 - slabs[0].s0);
     DevArray<DrawItem> d_items(cap);
@@ -4303,7 +4526,7 @@ void candidates_fetch(PairSet *set, Model *models, int64_t *model_offsets, int32
 void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
                 int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
                 const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
-                int64_t sample_chunk, int64_t model_chunk) {
+                int64_t sample_chunk, int64_t model_chunk, const DrawWeights *weights) {
     if (!set) throw std::invalid_argument("null pair set");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
@@ -4313,7 +4536,9 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
     if (!given && (sample_types || sample_idx))
         throw std::invalid_argument("sample_types / sample_idx without sample_offsets");
     if (!given) check_draw_args(num_sel, budget, point_share);
+    if (given && weights) throw std::invalid_argument("draw weights with given samples: nothing is drawn");
     std::lock_guard<std::mutex> lk(set->mu);
+    if (weights) check_draw_weights(set, weights);
     check_hyp_supported(set->variant, set->opts, set->cfg);
     if (set->num_pairs == 0) {
         std::vector<char> seen;
@@ -4353,6 +4578,7 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
     if (S > 0) {
         HypDraw dr{seed, share, nullptr};
         if (!given) dr.d_pair_n = set->pair_sizes(stream);
+        if (!given) bind_weights(dr, weights);
         HypBuffers B(v, S, sample_chunk, true, !given);
         hypothesize_run(R, stream, sel, soff, types, given ? sample_idx : nullptr, nullptr, counts.data(), sample_chunk,
                         B, timed, rt.hyp, given ? nullptr : &dr, &co);
@@ -4450,7 +4676,8 @@ void select_argmin_direct(int32_t num_pairs, const int64_t *model_offsets, const
 
 void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
-                         int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk) {
+                         int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk,
+                         const DrawWeights *weights) {
     if (!set) throw std::invalid_argument("null pair set");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
@@ -4460,6 +4687,7 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     // (a round obeys the bound a fixed-budget call obeys)
     check_draw_args(num_sel, std::min(step, budget), point_share);
     std::lock_guard<std::mutex> lk(set->mu);
+    if (weights) check_draw_weights(set, weights);
     check_hyp_supported(set->variant, set->opts, set->cfg);
     if (set->num_pairs == 0) {
         std::vector<char> seen;
@@ -4498,6 +4726,7 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
         // (the first round is the largest: its buffers serve every round)
         HypBuffers B(v, (int64_t)active.size() * std::min(step, budget), sample_chunk, true, true);
         HypDraw dr{seed, share, set->pair_sizes(stream), nullptr};
+        bind_weights(dr, weights);
         HypTiming htm;
         SelectTiming stm;
         std::vector<int32_t> ids, first, count, types, counts;
@@ -4577,7 +4806,7 @@ namespace {
 void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk, int32_t lo_steps, RansacLoStepsInfo *steps_info) {
+                   int64_t model_chunk, int32_t lo_steps, RansacLoStepsInfo *steps_info, const DrawWeights *weights) {
     if (!set) throw std::invalid_argument("null pair set");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (lo_rounds < 1 || lo_rounds > 64) throw std::invalid_argument("lo_rounds must be in 1..64");
@@ -4589,6 +4818,7 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
     // (a round obeys the bound a fixed-budget call obeys)
     check_draw_args(num_sel, std::min(step, budget), point_share);
     std::lock_guard<std::mutex> lk(set->mu);
+    if (weights) check_draw_weights(set, weights);
     check_hyp_supported(set->variant, set->opts, set->cfg);
     if (set->num_pairs == 0) {
         std::vector<char> seen;
@@ -4631,6 +4861,7 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
         // (the first round is the largest: its buffers serve every round)
         HypBuffers B(v, (int64_t)active.size() * std::min(step, budget), sample_chunk, true, true);
         HypDraw dr{seed, share, set->pair_sizes(stream), nullptr};
+        bind_weights(dr, weights);
         RefineBuffers lo_bufs(active.size(), true);
         R.lists(2); // (select takes one buffer, the LO both: no regrowth between the rounds)
         // With rounds = 0 the overall best's lists are the result's.  Both stages write their
@@ -4886,16 +5117,16 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
 void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk) {
+                   int64_t model_chunk, const DrawWeights *weights) {
     ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
-                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, 0, nullptr);
+                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, 0, nullptr, weights);
 }
 
 void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
                          Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
                          RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
-                         int64_t model_chunk) {
+                         int64_t model_chunk, const DrawWeights *weights) {
     if (!set) throw std::invalid_argument("null pair set");
     if (lo_steps < 1 || lo_steps > kLoStepsMax) throw std::invalid_argument("lo_steps must be in 1..64");
     if (num_sel > 0 && !steps_info) throw std::invalid_argument("null steps_info");
@@ -4904,7 +5135,7 @@ void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     if (!(set->opts.threshold_multiplier > 0.0) || !(set->opts.threshold_multiplier <= DBL_MAX))
         throw std::invalid_argument("threshold_multiplier must be positive and finite with lo_steps");
     ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
-                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, lo_steps, steps_info);
+                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, lo_steps, steps_info, weights);
 }
 
 void ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts, const int32_t *candidate,

@@ -204,6 +204,7 @@ HypTiming hypothesize_timing_last();
 // contexts go.  hypothesize_set: std::invalid_argument on a set whose variant or options
 // hypothesize_batch rejects.
 struct PairSet;
+struct DrawWeights; // (below, with draw_set)
 PairSet *pair_set_create(int variant, int32_t num_pairs, const int64_t *offsets, const double *x0, const double *x1,
                          const double *d0, const double *d1, const double *min_depth, const double *cam0,
                          const double *cam1, const RansacOptions &opts, const EstimatorConfig &cfg, int device);
@@ -312,8 +313,32 @@ struct RansacResult {
     int32_t lm_status; // as RefineResult; -1 without a winner or with rounds = 0
     int32_t num_inliers[3];
 };
+// Confidence-weighted sampling (mp_draw_weights_*, mp_draw_weighted_set, mp_ransac_weighted_set;
+// the rule: include/mp_draw.h, the kernels: kernels/draw_weighted.h).  draw_weights_create: one
+// launch builds the integer tables of the pairs given weights (given: num_pairs bytes, null: all;
+// weights: one value per correspondence of the set in set order, dtype 0 float32 / 1 float64, on
+// the host or -- on_device -- on the set's device, checked as pair_set_create_device checks its
+// arrays and ordered after producer_stream by an event).  std::invalid_argument: a weight that
+// is not finite in 0..1 (the lowest such row of the set is named), a pair above 65535
+// correspondences given weights, and the sets hypothesize_set refuses.  The handle is immutable,
+// belongs to `set` and lives outside it: draw_set / ransac_*_set with `weights` only read it, so a
+// call still leaves nothing in the set.  A pair whose positive weights number fewer than its
+// largest sample draws uniformly (weighted 0).  pair_set_destroy drops the handles' device
+// arrays; such a handle is refused by every call and may still be destroyed.
+// draw_weights_host / draw_weighted_host (mp_debug_*; no device): one pair's table (n + 1
+// entries) and count of positive weights; one sample of a weighted pair, draw_host's out.
+struct DrawWeights;
+DrawWeights *draw_weights_create(PairSet *set, const void *weights, int dtype, bool on_device,
+                                 const unsigned char *given, void *producer_stream);
+void draw_weights_info(const DrawWeights *w, int32_t *weighted, int32_t *positive, uint32_t *total);
+void draw_weights_destroy(DrawWeights *w); // null: nothing
+void draw_weights_host(int64_t n, const void *weights, int dtype, uint32_t *cum, int32_t *positive);
+void draw_weighted_host(int variant, int64_t n, const uint32_t *cum, uint64_t seed, int32_t point_share, int32_t pair,
+                        int32_t s, int32_t *out);
+// weights (here and in the ransac_*_set entries below; null: the uniform draw, today's launches)
 void draw_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
-              int32_t point_share, int32_t *sample_types, int32_t *sample_idx, int32_t *sample_counts);
+              int32_t point_share, int32_t *sample_types, int32_t *sample_idx, int32_t *sample_counts,
+              const DrawWeights *weights = nullptr);
 void draw_host(int variant, int64_t n, uint64_t seed, int32_t point_share, int32_t pair, int32_t s, int32_t *out);
 int64_t candidates_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
                        const int32_t *sample_types, const int32_t *sample_idx, int64_t sample_chunk);
@@ -321,7 +346,7 @@ void candidates_fetch(PairSet *set, Model *models, int64_t *model_offsets, int32
 void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
                 int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
                 const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
-                int64_t sample_chunk, int64_t model_chunk);
+                int64_t sample_chunk, int64_t model_chunk, const DrawWeights *weights = nullptr);
 // ransac_adaptive_set (mp_ransac_adaptive_set): ransac_set's drawn mode with a per-pair
 // number of samples.  Samples go through draw -> hypothesize_run -> select_run in rounds of
 // `step` per still-active pair (checkpoints m_k = min(k step, budget)); select_run continues
@@ -334,7 +359,8 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
 // counts and candidates are per round.  max_num_iterations is not read.
 void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
-                         int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk);
+                         int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk,
+                         const DrawWeights *weights = nullptr);
 // ransac_lo_set (mp_ransac_lo_set): ransac_adaptive_set with the estimators' local
 // optimisation prefix inside the rounds, two tracks per pair.  The minimal track is
 // ransac_adaptive_set's in every bit (select_run is seeded with the minimal best's score).
@@ -360,7 +386,7 @@ struct RansacLoInfo {
 void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk);
+                   int64_t model_chunk, const DrawWeights *weights = nullptr);
 // ransac_lo_steps_set (mp_ransac_lo_steps_set): ransac_lo_set with the num_lo_steps steps of the
 // estimators' LocalOptimization after each local optimisation (host/ransac_lo_steps.h): lo_steps
 // steps per entry whose minimal best was replaced, from the model the relaxed refinement
@@ -376,7 +402,7 @@ void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
                          uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
                          Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
                          RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
-                         int64_t model_chunk);
+                         int64_t model_chunk, const DrawWeights *weights = nullptr);
 // Test hook (mp_debug_ransac_lo_track; no device): host/ransac_lo_track.h walked over
 // num_rounds rounds in each of which the minimal best was replaced (its score and counts,
 // its candidate index, and its LO's rounds_accepted, score_final and counts).  score: the

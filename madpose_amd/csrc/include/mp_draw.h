@@ -102,4 +102,70 @@ MP_HD int draw_sample(int64_t n, int k_md, int k_pt, uint64_t seed, int point_sh
     return type;
 }
 
+// ---- the confidence-weighted draw (mp_draw_weights_create, mp_draw_weighted_set) ----
+// A pair given weights has the integer table q_i in 0 .. 65535 (the quantisation of the weights
+// is include/mp_draw_weights.h's; this header stays integer-only), c[0] = 0, c[i + 1] = c[i] +
+// q_i in uint32 and W = c[n]; n <= kDrawWeightMaxN, so W <= 65535^2 < 2^32.  q_i = 0 masks
+// correspondence i.  The pair is weighted iff #{q_i > 0} >= k_pt (n >= k_pt) or
+// k_md (n < k_pt); otherwise it draws by draw_sample.  The type is word 0's, unchanged.  From
+// word 1 on each word w proposes t = (uint64(w) * W) >> 32 (< W) and then the unique i with
+// c[i] <= t < c[i + 1] (so q_i > 0); slots and duplicates as draw_sample; the fill takes the
+// smallest unused indices with q_i > 0 in ascending order (there are at least k of them).
+// With all q_i equal to some q > 0: i = floor(floor(w n q / 2^32) / q) = floor(w n / 2^32),
+// draw_sample's proposal, so equal weights give draw_sample's bytes, fill included.
+constexpr int kDrawWeightMaxN = 65535;   // the largest pair that may be given weights
+constexpr uint32_t kDrawWeightQMax = 65535u;
+// draw_samples_weighted reads a table of at most this many entries (n + 1) through LDS: 16 KiB
+constexpr int kDrawStageEntries = 4096;
+
+// the pair's k_max: what #{q_i > 0} must reach for the pair to draw by its weights
+MP_HD int draw_weighted_need(int64_t n, int k_md, int k_pt) { return n >= k_pt ? k_pt : k_md; }
+
+// the i in 0 .. n - 1 with c[i] <= t < c[i + 1], for t < c[n] (c[0] = 0, c non-decreasing)
+MP_HD int draw_cum_find(const uint32_t *c, int n, uint32_t t) {
+    int lo = 0, hi = n; // c[lo] <= t < c[hi] throughout
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if (c[mid] <= t) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// draw_sample for a weighted pair: c its table of n + 1 entries (k_md <= n <= kDrawWeightMaxN,
+// at least draw_weighted_need of the q_i positive).  Every index written is < n.
+MP_HD int draw_sample_weighted(int n, int k_md, int k_pt, uint64_t seed, int point_share, uint32_t pair, uint32_t s,
+                               const uint32_t *c, int idx[8], bool *fill = nullptr) {
+    static_for<8>([&](auto I) { idx[I.value] = 0; });
+    if (fill) *fill = false;
+    if (n < k_md) return -1;
+    const uint32_t k0 = (uint32_t)seed, k1 = (uint32_t)(seed >> 32);
+    const uint64_t W = c[n];
+    uint32_t w[4];
+    philox4x32_10(s, 0u, pair, 0u, k0, k1, w);
+    const int type = draw_type_of(w[0], n, k_pt, point_share);
+    const int k = type ? k_pt : k_md;
+    int filled = 0;
+    auto propose = [&](int p) {
+        bool dup = false;
+        static_for<8>([&](auto I) { dup = dup || (I.value < filled && idx[I.value] == p); });
+        if (dup) return;
+        static_for<8>([&](auto I) {
+            if (I.value == filled) idx[I.value] = p;
+        });
+        ++filled;
+    };
+    for (int block = 0; block < kDrawBlocks && filled < k; ++block) {
+        if (block > 0) philox4x32_10(s, (uint32_t)block, pair, 0u, k0, k1, w);
+        for (int j = block == 0 ? 1 : 0; j < 4 && filled < k; ++j)
+            propose(draw_cum_find(c, n, (uint32_t)(((uint64_t)w[j] * W) >> 32)));
+    }
+    if (filled < k) {
+        if (fill) *fill = true;
+        for (int i = 0; i < n && filled < k; ++i)
+            if (c[i + 1] != c[i]) propose(i);
+    }
+    return type;
+}
+
 } // namespace mp

@@ -214,6 +214,21 @@ hipError_t launch_hyp_compact(hipStream_t s, int variant, const Model *models, c
 // samples[kSampleStride * (items[k].out + i) ..] and types[items[k].out + i].
 hipError_t launch_draw_samples(hipStream_t s, int variant, const DrawItem *items, int nitems, const int *pair_n,
                                uint64_t seed, int point_share, int *samples, int *types);
+// The confidence-weighted sampler (draw_weighted.h; include/mp_draw.h).  launch_draw_weights_table:
+// one launch over the set's pairs; pair p given weights (given null: every pair) of n = pair_n[p]
+// <= kDrawWeightMaxN values at weights + off[p] (dtype 0 float32, 1 float64) gets its table at cum +
+// off[p] + p (n + 1 entries), pos[p] = #{q > 0} and total[p] = W; *bad_row (set to INT_MAX before)
+// takes the lowest row of the set whose weight is refused.  launch_draw_samples_weighted:
+// launch_draw_samples with, for the pairs whose weighted[pair] is not 0, draw_sample_weighted on
+// the table at cum + cum_off[pair]; stage: tables of at most kDrawStageEntries entries are read
+// through LDS (the bytes do not depend on it).
+hipError_t launch_draw_weights_table(hipStream_t s, const void *weights, int dtype, const int64_t *off,
+                                     const int *pair_n, const unsigned char *given, int num_pairs, uint32_t *cum,
+                                     int *pos, uint32_t *total, int *bad_row);
+hipError_t launch_draw_samples_weighted(hipStream_t s, int variant, const DrawItem *items, int nitems,
+                                        const int *pair_n, const uint32_t *cum, const int64_t *cum_off,
+                                        const unsigned char *weighted, bool stage, uint64_t seed, int point_share,
+                                        int *samples, int *types);
 
 // squared Bougnoux focals of k fundamental matrices (9 doubles each) into out (2 each)
 hipError_t launch_bougnoux(hipStream_t s, const double *F, int64_t k, double *out);

@@ -1823,5 +1823,7 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 #include "hypothesize_batch.h"
 // the device sampler (mp_draw_set, mp_ransac_set)
 #include "draw_batch.h"
+// the confidence-weighted sampler (mp_draw_weights_create, mp_draw_weighted_set)
+#include "draw_weighted.h"
 // pair sets from arrays on the device (mp_pair_set_create_device)
 #include "ingest_pairs.h"
