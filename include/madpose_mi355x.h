@@ -227,6 +227,30 @@ int mp_debug_lm_refine_host(int variant, int64_t n, const double *x0, const doub
                             const int32_t *kinds, const int64_t *sample_offsets, const int32_t *sample_idx,
                             mp_model *models, int32_t *status);
 
+/* mp_debug_lm_system: one evaluation and one step of the same problems at their start
+ * models -- test hook of the LM's normal equations (tests/test_lm_system_*.py).  Pair,
+ * options, config, kinds, sample_offsets and sample_idx as mp_lm_refine_batch (no size
+ * rule: any lists); models[j] the point of evaluation, radius[j] the trust-region radius
+ * of the step.  where: 0 the device (the production kernels' setup, evaluation and step
+ * functions, one workgroup per problem), 1 / 2 the host's 4-wide (AVX2) / 8-wide (AVX-512)
+ * residual evaluation called directly over the blocks block_ranges[2j] .. block_ranges[2j+1]
+ * of the concatenated list (null or negative: all; the accumulators as they come), 3 the
+ * host LM's evaluate() (the compacted system, inactive entries zero); the host's step on
+ * the compacted system in all three.  where 2 without AVX-512 is MP_EINVAL.  Outputs per
+ * problem in the full 11-parameter layout (rotation tangent 3, t 3, scale, offset0,
+ * offset1, focal0, focal1; on the device entries past the variant's parameters are zero):
+ * cost, g[11] = J^T r, H[66] = the packed upper triangle of J^T J, col[11] = 1 for an
+ * active parameter, d[11] = the step (0 on inactive parameters), pd = 1 the damped system
+ * was positive definite, 0 it was not (d = 0), -1 nothing was evaluated (status 0 or 2 as
+ * mp_lm_refine_batch; everything else zero). */
+int mp_debug_lm_system(int variant, int64_t n, const double *x0, const double *x1, const double *d0, const double *d1,
+                       const double *min_depth, const double *cam0, const double *cam1,
+                       const mp_ransac_options *options, const mp_estimator_config *config, int32_t num_problems,
+                       const int32_t *kinds, const int64_t *sample_offsets, const int32_t *sample_idx,
+                       const mp_model *models, const double *radius, int32_t where, const int64_t *block_ranges,
+                       double *cost, double *g, double *H, int32_t *col, double *d, int32_t *pd, int32_t *status,
+                       int device);
+
 /* Device refinement of given poses over many pairs: for callers who have a pose already
  * (a previous frame, a regressor, another estimator, an earlier run with other
  * thresholds) and want it polished with the estimators' depth-aware cost.  The

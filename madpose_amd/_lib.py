@@ -354,6 +354,12 @@ EXPORTS = {
                                                ctypes.POINTER(mp_ransac_options), ctypes.POINTER(mp_estimator_config),
                                                ctypes.c_int32, c_int32_p, c_int64_p, c_int32_p,
                                                ctypes.POINTER(mp_model), c_int32_p]),
+    "mp_debug_lm_system": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, c_double_p, c_double_p, c_double_p,
+                                          c_double_p, c_double_p, c_double_p, c_double_p,
+                                          ctypes.POINTER(mp_ransac_options), ctypes.POINTER(mp_estimator_config),
+                                          ctypes.c_int32, c_int32_p, c_int64_p, c_int32_p, ctypes.POINTER(mp_model),
+                                          c_double_p, ctypes.c_int32, c_int64_p, c_double_p, c_double_p, c_double_p,
+                                          c_int32_p, c_double_p, c_int32_p, c_int32_p, ctypes.c_int]),
     "mp_bougnoux_focals": (ctypes.c_int, [ctypes.c_int64, c_double_p, c_double_p, ctypes.c_int]),
     "mp_pose_eval": (ctypes.c_int, [ctypes.c_int64, c_double_p, c_double_p, c_double_p, ctypes.c_double, c_double_p,
                                     c_double_p, ctypes.c_int32, c_double_p, c_double_p, ctypes.c_int]),

@@ -730,6 +730,57 @@ def lm_refine_batch(variant, x0, x1, depth0, depth1, min_depth, cam0, cam1, opti
     return [(_model_from_c(models[j], variant), int(status[j])) for j in range(P)]
 
 
+def lm_system(variant, x0, x1, depth0, depth1, min_depth, cam0, cam1, options, est_config, problems, radius,
+              where=0, block_ranges=None, device=None):
+    """One evaluation and one step of lm_refine_batch's problems at their start models -- test
+    hook (mp_debug_lm_system).  radius: one trust-region radius, or one per problem; where: 0
+    the device, 1 / 2 the host's 4- / 8-wide residual evaluation (block_ranges: optional
+    (b0, b1) per problem over the concatenated block list), 3 the host LM's evaluate().
+    Returns a dict of arrays over the problems in the full 11-parameter layout: cost (P), g
+    (P, 11), H (P, 66: packed upper triangle), col (P, 11), d (P, 11), pd (P: 1 positive
+    definite, 0 not, -1 nothing evaluated) and status (P)."""
+    if est_config is None:
+        est_config = EstimatorConfig()
+    x0 = _pts(x0, "x0")
+    n = x0.shape[0]
+    x1 = _pts(x1, "x1")
+    d0, d1 = _vec(depth0, n, "depth0"), _vec(depth1, n, "depth1")
+    md = np.asarray(min_depth, dtype=np.float64).reshape(2)
+    k = 9 if variant in (L.CALIBRATED, L.SCALE_ONLY) else 2
+    c0 = np.ascontiguousarray(np.asarray(cam0, dtype=np.float64).reshape(k))
+    c1 = np.ascontiguousarray(np.asarray(cam1, dtype=np.float64).reshape(k))
+    P = len(problems)
+    kinds = np.array([int(p[0]) for p in problems] or [0], dtype=np.int32)
+    offs, idx = [0], []
+    for _, lists, _m in problems:
+        for t in range(3):
+            a = np.asarray(lists[t], dtype=np.int32).reshape(-1)
+            idx.append(a)
+            offs.append(offs[-1] + len(a))
+    offs = np.asarray(offs, dtype=np.int64)
+    idx = np.ascontiguousarray(np.concatenate(idx) if idx and offs[-1] > 0 else np.zeros(1, dtype=np.int32))
+    models = (L.mp_model * max(P, 1))()
+    for j, (_, _, m) in enumerate(problems):
+        models[j] = _model_to_c(m, variant)
+    rad = np.ascontiguousarray(np.broadcast_to(np.asarray(radius, dtype=np.float64), (max(P, 1),)))
+    rng = None
+    if block_ranges is not None:
+        rng = np.ascontiguousarray(np.asarray(block_ranges, dtype=np.int64).reshape(max(P, 1), 2))
+    out = dict(cost=np.zeros(max(P, 1)), g=np.zeros((max(P, 1), 11)), H=np.zeros((max(P, 1), 66)),
+               col=np.zeros((max(P, 1), 11), dtype=np.int32), d=np.zeros((max(P, 1), 11)),
+               pd=np.zeros(max(P, 1), dtype=np.int32), status=np.zeros(max(P, 1), dtype=np.int32))
+    o = options._to_c()
+    c = est_config._to_c()
+    i32 = lambda a: a.ctypes.data_as(L.c_int32_p)
+    L.check(L.lib().mp_debug_lm_system(
+        variant, n, _dp(x0), _dp(x1), _dp(d0), _dp(d1), _dp(md), _dp(c0), _dp(c1), ctypes.byref(o), ctypes.byref(c), P,
+        i32(kinds), offs.ctypes.data_as(L.c_int64_p), i32(idx), models, _dp(rad), int(where),
+        None if rng is None else rng.ctypes.data_as(L.c_int64_p), _dp(out["cost"]), _dp(out["g"]), _dp(out["H"]),
+        i32(out["col"]), _dp(out["d"]), i32(out["pd"]), i32(out["status"]),
+        _DEFAULT_DEVICE if device is None else int(device)))
+    return {k: v[:P] for k, v in out.items()}
+
+
 def bougnoux_focals_batch(F, device=None):
     """Squared Bougnoux focal lengths (f0^2, f1^2) of fundamental matrices F (k x 3 x 3,
     principal points at the origin) on the device: the two-focal 7-point tail's own

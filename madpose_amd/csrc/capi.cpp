@@ -972,6 +972,39 @@ int mp_debug_lm_refine_host(int variant, int64_t n, const double *x0, const doub
                             });
 }
 
+int mp_debug_lm_system(int variant, int64_t n, const double *x0, const double *x1, const double *d0, const double *d1,
+                       const double *min_depth, const double *cam0, const double *cam1,
+                       const mp_ransac_options *options, const mp_estimator_config *config, int32_t num_problems,
+                       const int32_t *kinds, const int64_t *sample_offsets, const int32_t *sample_idx,
+                       const mp_model *models, const double *radius, int32_t where, const int64_t *block_ranges,
+                       double *cost, double *g, double *H, int32_t *col, double *d, int32_t *pd, int32_t *status,
+                       int device) {
+    return guarded([&]() {
+        if (!options || num_problems < 0 ||
+            (num_problems > 0 && (!sample_offsets || !models || !radius || !cost || !g || !H || !col || !d || !pd ||
+                                  !status)))
+            throw std::invalid_argument("bad arguments");
+        if (num_problems > 0 && sample_offsets[3 * num_problems] > 0 && !sample_idx)
+            throw std::invalid_argument("null sample indices");
+        const double md0[2] = {0.0, 0.0};
+        mp::PairInput in = make_input(variant, n, x0, x1, d0, d1, min_depth ? min_depth : md0, cam0, cam1);
+        std::vector<mp::Model> ms(num_problems);
+        if (num_problems > 0) std::memcpy(ms.data(), models, sizeof(mp_model) * num_problems);
+        std::vector<mp::LmSystem> sys(num_problems);
+        mp::lm_system_batch(in, to_opts(options), to_cfg(config), num_problems, kinds, sample_offsets, sample_idx,
+                            ms.data(), radius, where, block_ranges, sys.data(), status, device);
+        for (int j = 0; j < num_problems; ++j) {
+            cost[j] = sys[j].cost;
+            std::memcpy(g + 11 * j, sys[j].g, sizeof(sys[j].g));
+            std::memcpy(H + 66 * j, sys[j].H, sizeof(sys[j].H));
+            std::memcpy(d + 11 * j, sys[j].d, sizeof(sys[j].d));
+            for (int a = 0; a < 11; ++a) col[11 * j + a] = sys[j].col[a];
+            pd[j] = sys[j].pd;
+        }
+        return MP_OK;
+    });
+}
+
 static int point_direct(int kind, const double *x1, const double *x2, mp_model *out, int max_out, int device) {
     if (!x1 || !x2 || (max_out > 0 && !out)) return -fail(MP_EINVAL, "null argument");
     int r = guarded([&]() {

@@ -2444,6 +2444,21 @@ void validate_lm_batch(const PairInput &in, int nprob, const int64_t *offsets, c
     for (int64_t k = offsets[0]; k < offsets[3 * (int64_t)nprob]; ++k)
         if (idx[k] < 0 || idx[k] >= in.n) throw std::invalid_argument("sample index out of range");
 }
+// the host LM's settings of a job (the same Ceres settings as the device LM reads from it)
+LMSettings lm_settings(const EstimatorConfig &cfg, const LmJob &J) {
+    LMSettings S;
+    S.use_reproj = cfg.lo_type != 1;
+    S.use_sampson = cfg.lo_type != 2;
+    S.use_shift = J.use_shift != 0;
+    S.min_depth_constraint = J.min_depth_constraint != 0;
+    S.w_sampson = J.w_sampson;
+    S.ftol = J.ftol;
+    S.gtol = J.gtol;
+    S.ptol = J.ptol;
+    S.max_iter = J.max_iter;
+    S.nonmonotonic = J.nonmonotonic != 0;
+    return S;
+}
 } // namespace
 
 // the same problems through the host LM (host/lm.cpp) -- test hook (mp_debug_lm_refine_host);
@@ -2468,17 +2483,7 @@ void lm_refine_batch_host(const PairInput &in, const RansacOptions &opts, const 
             continue;
         }
         const LmJob J = make_lm_job(P, cfg, sz, 0, kinds && kinds[j] == 1, models[j]);
-        LMSettings S;
-        S.use_reproj = cfg.lo_type != 1;
-        S.use_sampson = cfg.lo_type != 2;
-        S.use_shift = J.use_shift != 0;
-        S.min_depth_constraint = J.min_depth_constraint != 0;
-        S.w_sampson = J.w_sampson;
-        S.ftol = J.ftol;
-        S.gtol = J.gtol;
-        S.ptol = J.ptol;
-        S.max_iter = J.max_iter;
-        S.nonmonotonic = J.nonmonotonic != 0;
+        const LMSettings S = lm_settings(cfg, J);
         status[j] = lm_refine(P.H, smp, S, &models[j]) ? 1 : 0;
     }
 }
@@ -2527,6 +2532,60 @@ void lm_refine_batch_device(const PairInput &in, const RansacOptions &opts, cons
         models[which[k]] = out[k];
         status[which[k]] = st[k];
     }
+}
+
+// One evaluation and one step of every problem at its start model -- test hook
+// (mp_debug_lm_system).  No size rule: any lists, empty ones included.  where 0: the
+// device (lm_system_kernel), 1 / 2: the host's 4- / 8-wide residual evaluation over the
+// block range ranges[2j], ranges[2j + 1] (null or negative: all blocks), 3: the host LM's
+// evaluate().
+void lm_system_batch(const PairInput &in, const RansacOptions &opts, const EstimatorConfig &cfg, int nprob,
+                     const int32_t *kinds, const int64_t *offsets, const int32_t *idx, const Model *models,
+                     const double *radius, int where, const int64_t *ranges, LmSystem *out, int32_t *status,
+                     int device) {
+    validate(in, opts);
+    validate_lm_batch(in, nprob, offsets, idx, models, status);
+    if (!radius || !out) throw std::invalid_argument("null radius or output");
+    if (where < 0 || where > 3) throw std::invalid_argument("where must be 0..3");
+    if (where == 2 && !lm_debug_have_w8()) throw std::invalid_argument("no AVX-512 on this CPU");
+    if (nprob <= 0) return;
+    Problem P = make_problem(in, opts, cfg);
+    std::vector<LmJob> jobs;
+    for (int j = 0; j < nprob; ++j) {
+        int sz[3];
+        for (int t = 0; t < 3; ++t) sz[t] = (int)(offsets[3 * j + t + 1] - offsets[3 * j + t]);
+        jobs.push_back(make_lm_job(P, cfg, sz, (int)offsets[3 * j], kinds && kinds[j] == 1, models[j]));
+    }
+    if (where != 0) {
+        for (int j = 0; j < nprob; ++j) {
+            std::vector<int> smp[3];
+            for (int t = 0; t < 3; ++t) smp[t].assign(idx + offsets[3 * j + t], idx + offsets[3 * j + t + 1]);
+            lm_debug_system(P.H, smp, lm_settings(cfg, jobs[j]), models[j], radius[j], where,
+                            ranges ? (long long)ranges[2 * j] : -1, ranges ? (long long)ranges[2 * j + 1] : -1, &out[j]);
+            const int nb = jobs[j].n0 + jobs[j].n1 + jobs[j].n2;
+            status[j] = nb == 0 ? 0 : (out[j].pd < 0 ? 2 : 1);
+        }
+        return;
+    }
+    CtxLease lease(device);
+    DeviceCtx &X = *lease.c;
+    X.ensure(in.n, 64, max_models(in.variant == kScaleOnly ? kCal : in.variant));
+    PairData D;
+    upload_pair(X, P, &D);
+    const int64_t nidx = offsets[3 * nprob];
+    DevArray<LmJob> d_jobs(jobs.size());
+    DevArray<int> d_idx((size_t)std::max<int64_t>(nidx, 1)), d_status(jobs.size());
+    DevArray<double> d_radius(jobs.size());
+    DevArray<LmSystem> d_sys(jobs.size());
+    MP_HIP(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(LmJob) * jobs.size(), hipMemcpyHostToDevice, X.stream));
+    MP_HIP(hipMemcpyAsync(d_radius.p, radius, sizeof(double) * jobs.size(), hipMemcpyHostToDevice, X.stream));
+    if (nidx > 0) MP_HIP(hipMemcpyAsync(d_idx.p, idx, sizeof(int) * nidx, hipMemcpyHostToDevice, X.stream));
+    MP_HIP(launch_lm_system(X.stream, D, P.C, d_jobs.p, (int)jobs.size(), d_idx.p, d_radius.p, d_sys.p, d_status.p));
+    std::vector<int> st(jobs.size());
+    MP_HIP(hipMemcpyAsync(out, d_sys.p, sizeof(LmSystem) * jobs.size(), hipMemcpyDeviceToHost, X.stream));
+    MP_HIP(hipMemcpyAsync(st.data(), d_status.p, sizeof(int) * st.size(), hipMemcpyDeviceToHost, X.stream));
+    MP_HIP(hipStreamSynchronize(X.stream));
+    for (int j = 0; j < nprob; ++j) status[j] = st[j];
 }
 
 #include "resident_pairs.h"

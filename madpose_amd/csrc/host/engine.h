@@ -98,6 +98,11 @@ void lm_refine_batch_device(const PairInput &in, const RansacOptions &opts, cons
 void lm_refine_batch_host(const PairInput &in, const RansacOptions &opts, const EstimatorConfig &cfg, int nprob,
                           const int32_t *kinds, const int64_t *offsets, const int32_t *idx, Model *models,
                           int32_t *status);
+// One evaluation and one step per problem -- test hook (mp_debug_lm_system; engine.cpp)
+void lm_system_batch(const PairInput &in, const RansacOptions &opts, const EstimatorConfig &cfg, int nprob,
+                     const int32_t *kinds, const int64_t *offsets, const int32_t *idx, const Model *models,
+                     const double *radius, int where, const int64_t *ranges, LmSystem *out, int32_t *status,
+                     int device);
 
 // Device refinement of given models over many pairs (mp_refine_batch).  Pairs laid out
 // as mp_estimate_batch's (offsets, 2 min depths and 9 / 2 camera values per pair); models:

@@ -103,7 +103,9 @@ struct Acc {
 // comparable to a thread wake-up) run inline.  MADPOSE_LO_THREADS sets the pool size
 // (default 8, of which 4 take the problems below kPoolWide blocks; 1 = off).  The
 // blocks are reduced in fixed chunks in chunk order either way, so the result does not
-// depend on the pool.
+// depend on the pool (tests/test_lm_system_cpu.py::test_switches_do_not_change_the_host_lm:
+// identical bytes under MADPOSE_LO_THREADS = 1 and 8, MADPOSE_LM_WIDE = 1 and either ISA;
+// test_evaluate_chunks_and_pool: the sums on both sides of the pool and stack / heap limits).
 constexpr size_t kChunk = 256;
 constexpr size_t kPoolBlocks = 2048;
 // Workers spin (with pause) for a while after each job before they block on the
@@ -264,7 +266,8 @@ Pool &lo_pool() {
 }
 
 // the 8-lane residual evaluation runs as AVX-512 when the CPU has it (identical results
-// either way, lm_eval.inc); MADPOSE_LM_ISA=avx2 forces the AVX2 build (A/B)
+// either way, lm_eval.inc: tests/test_lm_system_cpu.py::test_w4_equals_w8_bytes);
+// MADPOSE_LM_ISA=avx2 forces the AVX2 build (A/B)
 bool lm_eval_avx512() {
     static const bool on = [] {
         if (env_avx2("MADPOSE_LM_ISA")) return false;
@@ -280,17 +283,9 @@ size_t num_blocks(const Ctx &C) {
            (C.S.use_sampson ? C.sample[2].size() : 0);
 }
 
-// Evaluates cost (and, when H != nullptr, the active normal equations) at p.  Blocks
-// are reduced in fixed chunks in chunk order, so the result does not depend on how
-// many worker threads evaluate them.
-double evaluate(const Ctx &C, const Params &p, double *H, double *g) {
-    const size_t nb = num_blocks(C);
-    const size_t nchunks = (nb + kChunk - 1) / kChunk;
-    const bool jac = H != nullptr;
-    Acc total;
-    total.clear();
+// the residual evaluation's view of a problem and of a parameter set (lm_eval.h)
+void eval_inputs(const Ctx &C, const Params &p, LmEvalIn &E, LmEvalParams &ep) {
     const HostPair &P = *C.P;
-    LmEvalIn E;
     E.variant = P.variant;
     E.x0 = P.x0.data();
     E.x1 = P.x1.data();
@@ -307,7 +302,6 @@ double evaluate(const Ctx &C, const Params &p, double *H, double *g) {
     E.n1 = C.S.use_reproj ? C.sample[1].size() : 0;
     E.n2 = C.S.use_sampson ? C.sample[2].size() : 0;
     E.w_sampson = C.S.w_sampson;
-    LmEvalParams ep;
     std::memcpy(ep.R, p.R, sizeof(ep.R));
     std::memcpy(ep.t, p.t, sizeof(ep.t));
     ep.s = p.s;
@@ -315,6 +309,20 @@ double evaluate(const Ctx &C, const Params &p, double *H, double *g) {
     ep.o1 = p.o1;
     ep.f0 = p.f0;
     ep.f1 = p.f1;
+}
+
+// Evaluates cost (and, when H != nullptr, the active normal equations) at p.  Blocks
+// are reduced in fixed chunks in chunk order, so the result does not depend on how
+// many worker threads evaluate them.
+double evaluate(const Ctx &C, const Params &p, double *H, double *g) {
+    const size_t nb = num_blocks(C);
+    const size_t nchunks = (nb + kChunk - 1) / kChunk;
+    const bool jac = H != nullptr;
+    Acc total;
+    total.clear();
+    LmEvalIn E;
+    LmEvalParams ep;
+    eval_inputs(C, p, E, ep);
     const auto eval = lm_eval_avx512() ? lm_eval_range_w8 : lm_eval_range_w4;
     auto range = [&](size_t a, size_t b, Acc &acc) { eval(E, ep, jac, a, b, acc.H, acc.g, &acc.cost); };
     if (nchunks <= 1) {
@@ -366,6 +374,25 @@ bool chol_solve(double *A, int n, double *b) {
     return true;
 }
 
+// The LM step of the compacted system (H n x n, g): Jacobi column scaling, the LM
+// diagonal clamped to [1e-6, 1e32] over the radius, Cholesky.  False when the damped
+// system is not positive definite (d untouched).
+bool lm_step(const double *H, const double *g, int n, double radius, double *d) {
+    double sc[kNFull], A[kNFull * kNFull], y[kNFull];
+    for (int j = 0; j < n; ++j) sc[j] = 1.0 / (1.0 + std::sqrt(H[j * n + j]));
+    for (int a = 0; a < n; ++a) {
+        y[a] = -g[a] * sc[a];
+        for (int b = 0; b < n; ++b) A[a * n + b] = H[a * n + b] * sc[a] * sc[b];
+    }
+    for (int j = 0; j < n; ++j) {
+        const double dg = std::min(std::max(A[j * n + j], 1e-6), 1e32);
+        A[j * n + j] += dg / radius;
+    }
+    if (!chol_solve(A, n, y)) return false;
+    for (int j = 0; j < n; ++j) d[j] = y[j] * sc[j];
+    return true;
+}
+
 void set_rotation(Params &p) { quat_to_rot(p.q, p.R); }
 
 } // namespace
@@ -411,25 +438,36 @@ void quat_to_rot(const double *q0, double *R) {
     R[8] = 1 - 2 * (x * x + y * y);
 }
 
-thread_local int lm_last_evals = 0;
-
-bool lm_refine(const HostPair &P, const std::vector<int> *sample, const LMSettings &S, Model *m) {
-    lm_last_evals = 0;
+namespace {
+// The set-up of one problem: the active columns (Ceres' constant parameter blocks
+// dropped), the lower bounds and the start parameters.  Returns 0 without residuals, 2
+// when a constant bounded block starts infeasible, else 1.
+struct Setup {
     Ctx C;
+    bool has_lo[kNFull];
+    double lo[kNFull];
+    Params x;
+};
+int lm_setup(const HostPair &P, const std::vector<int> *sample, const LMSettings &S, const Model &m, Setup &U) {
+    Ctx &C = U.C;
     C.P = &P;
     C.sample = sample;
     C.S = S;
     size_t nres = 0;
     if (S.use_reproj) nres += sample[0].size() + sample[1].size();
     if (S.use_sampson) nres += sample[2].size();
-    if (nres == 0) return false;
+    if (nres == 0) return 0;
     C.has_o0 = S.use_reproj && !sample[0].empty();
     C.has_s_o1 = S.use_reproj && !sample[1].empty();
     for (int k = 0; k < kNFull; ++k) C.col[k] = -1;
     int n = 0;
     for (int k = 0; k < 6; ++k) C.col[k] = n++;
-    bool has_lo[kNFull] = {false};
-    double lo[kNFull] = {0};
+    bool *has_lo = U.has_lo;
+    double *lo = U.lo;
+    for (int k = 0; k < kNFull; ++k) {
+        has_lo[k] = false;
+        lo[k] = 0.0;
+    }
     if (C.has_s_o1) {
         C.col[kS] = n++;
         has_lo[kS] = true;
@@ -450,20 +488,38 @@ bool lm_refine(const HostPair &P, const std::vector<int> *sample, const LMSettin
         lo[kF0] = lo[kF1] = 1e-6;
     }
     C.n = n;
-    Params x;
-    rot_to_quat(m->R, x.q);
+    Params &x = U.x;
+    rot_to_quat(m.R, x.q);
     set_rotation(x);
-    std::memcpy(x.t, m->t, sizeof(x.t));
-    x.s = m->scale;
-    x.o0 = m->offset0;
-    x.o1 = m->offset1;
-    x.f0 = m->focal0;
-    x.f1 = m->focal1;
+    std::memcpy(x.t, m.t, sizeof(x.t));
+    x.s = m.scale;
+    x.o0 = m.offset0;
+    x.o1 = m.offset1;
+    x.f0 = m.focal0;
+    x.f1 = m.focal1;
     // constant bounded blocks must start feasible (Ceres Program::IsFeasible)
     if (!S.use_shift && S.min_depth_constraint) {
-        if (C.has_o0 && x.o0 < lo[kO0]) return true;
-        if (C.has_s_o1 && x.o1 < lo[kO1]) return true;
+        if (C.has_o0 && x.o0 < lo[kO0]) return 2;
+        if (C.has_s_o1 && x.o1 < lo[kO1]) return 2;
     }
+    return 1;
+}
+
+} // namespace
+
+thread_local int lm_last_evals = 0;
+
+bool lm_refine(const HostPair &P, const std::vector<int> *sample, const LMSettings &S, Model *m) {
+    lm_last_evals = 0;
+    Setup U;
+    const int ready = lm_setup(P, sample, S, *m, U);
+    if (ready == 0) return false;
+    if (ready == 2) return true;
+    const Ctx &C = U.C;
+    const int n = C.n;
+    const bool *has_lo = U.has_lo;
+    const double *lo = U.lo;
+    Params x = U.x;
     auto amb_norm2 = [](const Params &p) {
         return p.q[0] * p.q[0] + p.q[1] * p.q[1] + p.q[2] * p.q[2] + p.q[3] * p.q[3] + p.t[0] * p.t[0] +
                p.t[1] * p.t[1] + p.t[2] * p.t[2] + p.s * p.s + p.o0 * p.o0 + p.o1 * p.o1 + p.f0 * p.f0 + p.f1 * p.f1;
@@ -491,24 +547,13 @@ bool lm_refine(const HostPair &P, const std::vector<int> *sample, const LMSettin
     Params best = x;
     if (!(gmax() <= S.gtol)) {
         for (int iter = 0; iter < S.max_iter; ++iter) {
-            double sc[kNFull], A[kNFull * kNFull], y[kNFull];
-            for (int j = 0; j < n; ++j) sc[j] = 1.0 / (1.0 + std::sqrt(H[j * n + j]));
-            for (int a = 0; a < n; ++a) {
-                y[a] = -g[a] * sc[a];
-                for (int b = 0; b < n; ++b) A[a * n + b] = H[a * n + b] * sc[a] * sc[b];
-            }
-            for (int j = 0; j < n; ++j) {
-                const double dg = std::min(std::max(A[j * n + j], 1e-6), 1e32);
-                A[j * n + j] += dg / radius;
-            }
-            if (!chol_solve(A, n, y)) {
+            double d[kNFull];
+            if (!lm_step(H, g, n, radius, d)) {
                 radius /= decrease;
                 decrease *= 2.0;
                 if (radius < 1e-32) break;
                 continue;
             }
-            double d[kNFull];
-            for (int j = 0; j < n; ++j) d[j] = y[j] * sc[j];
             // candidate = Plus(x, d), projected onto the bounds
             Params c = x;
             {
@@ -602,6 +647,55 @@ bool lm_refine(const HostPair &P, const std::vector<int> *sample, const LMSettin
     m->focal0 = best.f0;
     m->focal1 = (P.variant == kSF) ? best.f0 : best.f1;
     return true;
+}
+
+void lm_debug_system(const HostPair &P, const std::vector<int> *sample, const LMSettings &S, const Model &m,
+                     double radius, int where, long long b0, long long b1, LmSystem *out) {
+    std::memset(out, 0, sizeof(*out));
+    out->pd = -1;
+    Setup U;
+    const int ready = lm_setup(P, sample, S, m, U);
+    if (ready == 0) return;
+    const Ctx &C = U.C;
+    const int n = C.n;
+    for (int a = 0; a < kNFull; ++a) out->col[a] = C.col[a] >= 0 ? 1 : 0;
+    if (ready == 2) return;
+    double H[kNFull * kNFull], g[kNFull];
+    if (where == 3) {
+        // the compacted system as lm_refine gets it, spread back over the full layout
+        out->cost = evaluate(C, U.x, H, g);
+        for (int a = 0; a < kNFull; ++a) {
+            if (C.col[a] < 0) continue;
+            out->g[a] = g[C.col[a]];
+            for (int b = a; b < kNFull; ++b)
+                if (C.col[b] >= 0) out->H[a * kNFull - a * (a - 1) / 2 + (b - a)] = H[C.col[a] * n + C.col[b]];
+        }
+    } else {
+        // one call of the residual evaluation over blocks [b0, b1): its accumulators as they are
+        LmEvalIn E;
+        LmEvalParams ep;
+        eval_inputs(C, U.x, E, ep);
+        const size_t nb = num_blocks(C);
+        const size_t lo = b0 < 0 ? 0 : std::min((size_t)b0, nb), hi = b1 < 0 ? nb : std::min((size_t)b1, nb);
+        Acc acc;
+        acc.clear();
+        (where == 2 ? lm_eval_range_w8 : lm_eval_range_w4)(E, ep, true, lo, std::max(lo, hi), acc.H, acc.g, &acc.cost);
+        out->cost = acc.cost;
+        std::memcpy(out->H, acc.H, sizeof(acc.H));
+        std::memcpy(out->g, acc.g, sizeof(acc.g));
+        acc.scatter(C, H, g);
+    }
+    double d[kNFull];
+    const bool ok = lm_step(H, g, n, radius, d);
+    out->pd = ok ? 1 : 0;
+    if (ok)
+        for (int a = 0; a < kNFull; ++a)
+            if (C.col[a] >= 0) out->d[a] = d[C.col[a]];
+}
+
+bool lm_debug_have_w8() {
+    __builtin_cpu_init();
+    return __builtin_cpu_supports("avx512f") && __builtin_cpu_supports("avx512dq") && __builtin_cpu_supports("avx512vl");
 }
 
 } // namespace mp

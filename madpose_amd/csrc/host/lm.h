@@ -42,6 +42,16 @@ bool lm_refine(const HostPair &P, const std::vector<int> *sample, const LMSettin
 // normal-equation evaluations of this thread's last lm_refine (MADPOSE_LO_TIMING)
 extern thread_local int lm_last_evals;
 
+// One evaluation and one step at m -- test hook (mp_debug_lm_system): lm_refine's set-up,
+// then the normal equations by `where` (1: lm_eval_range_w4 over blocks [b0, b1) of the
+// concatenated list, 2: lm_eval_range_w8 likewise, the accumulators as they come; 3:
+// evaluate() as lm_refine calls it, the compacted system spread back over the full
+// layout), then lm_refine's step on the compacted system with `radius`.  b0 / b1 < 0: the
+// whole list.
+void lm_debug_system(const HostPair &P, const std::vector<int> *sample, const LMSettings &S, const Model &m,
+                     double radius, int where, long long b0, long long b1, LmSystem *out);
+bool lm_debug_have_w8(); // the CPU runs lm_eval_range_w8 (AVX-512 F, DQ, VL)
+
 // the LM pool's spin before blocking, in microseconds (MADPOSE_LO_SPIN, or the
 // affinity-based default of lm.cpp)
 int lo_spin_us();

@@ -1,6 +1,8 @@
 // Residual-block evaluation of the host LM (lm.cpp), built twice: for x86-64-v4
 // (AVX-512) and x86-64-v3 (AVX2).  The two builds share one source (lm_eval.inc) and
-// give identical results; lm.cpp calls the AVX-512 one when the CPU has it.
+// give identical results (tests/test_lm_system_cpu.py::test_w4_equals_w8_bytes; both are
+// held to a 50-digit reference there, and tests/lm_eval_check.cpp runs their tails under
+// AddressSanitizer); lm.cpp calls the AVX-512 one when the CPU has it.
 #pragma once
 #include <cstddef>
 

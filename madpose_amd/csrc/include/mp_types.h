@@ -121,6 +121,16 @@ struct LmJob {
     Model m;
 };
 
+// One evaluation and one step of a problem (mp_debug_lm_system; kernels/lm_device.h
+// lm_system_kernel, host/lm.cpp lm_debug_system), in the full 11-parameter layout: the
+// cost, J^T r, the packed upper triangle of J^T J, the active-column mask, the step for
+// the given radius and pd = 1 (the damped system was positive definite), 0 (it was not:
+// d = 0) or -1 (nothing evaluated: no residuals or an infeasible constant block).
+struct LmSystem {
+    double cost, g[11], H[66], d[11];
+    int col[11], pd;
+};
+
 // Many resident pairs per launch (kernels/refine_batch.h, lm_pairs_kernel): the pairs'
 // PairData / PairConst records sit in device arrays and a work item names its pair.
 // LmPairRef: beside LmJob j, the pair of the job and where its block lists start (ints

@@ -137,6 +137,10 @@ hipError_t launch_sb_pt7(hipStream_t s, const double *in, int ld, int ns, double
 // refined, 0 no residuals, 2 infeasible constant block (unchanged)
 hipError_t launch_lm_batch(hipStream_t s, const PairData &D, const PairConst &C, const LmJob *jobs, int njobs,
                            const int *idx, Model *out, int *status);
+// one evaluation and one step of each job at its start model with radius[j] -- test hook
+// (mp_debug_lm_system): sys[j] in the full layout, status[j] as above
+hipError_t launch_lm_system(hipStream_t s, const PairData &D, const PairConst &C, const LmJob *jobs, int njobs,
+                            const int *idx, const double *radius, LmSystem *sys, int *status);
 
 // Many resident pairs per launch (refine_batch.h; mp_refine_batch).  Ds / Cs: one record
 // per pair in device memory; variant: the pairs' common PairConst::variant.

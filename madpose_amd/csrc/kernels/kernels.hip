@@ -1629,6 +1629,15 @@ hipError_t launch_lm_batch(hipStream_t s, const PairData &D, const PairConst &C,
     });
 }
 
+hipError_t launch_lm_system(hipStream_t s, const PairData &D, const PairConst &C, const LmJob *jobs, int njobs,
+                            const int *idx, const double *radius, LmSystem *sys, int *status) {
+    if (njobs <= 0) return hipSuccess;
+    return by_variant(C.variant, [&](auto V) {
+        lm_system_kernel<decltype(V)::value><<<njobs, kLmBlock, 0, s>>>(D, C, jobs, idx, radius, sys, status);
+        return hipGetLastError();
+    });
+}
+
 hipError_t launch_bougnoux(hipStream_t s, const double *F, int64_t k, double *out) {
     if (k <= 0) return hipSuccess;
     bougnoux_kernel<<<(int)((k + 255) / 256), 256, 0, s>>>(F, k, out);

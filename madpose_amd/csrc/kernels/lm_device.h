@@ -419,7 +419,9 @@ constexpr int kLmBlock = 256;
 // NA-parameter layout (packed upper triangle, then g, then the cost); parameters that
 // are inactive for the call are masked to an identity row with zero gradient, which
 // leaves every operation on the active ones exactly as in the compacted system of
-// host/lm.cpp (the extra terms are exact zeros).
+// host/lm.cpp (the extra terms are exact zeros: tests/test_lm_system_gpu.py
+// test_formulas_against_50_digits holds the zero entries to 0.0, test_step_backward_error
+// the step to the active system alone, with d = 0 on the masked parameters).
 template <int NA> struct LmShared {
     static constexpr int kPack = NA * (NA + 1) / 2, kRed = kPack + NA + 1;
     LmParams x, c, best;
@@ -591,6 +593,47 @@ __global__ void __launch_bounds__(kLmBlock) __attribute__((flatten))
     const PairConst &C = Cs[ref.pair];
     const int *idx = idx_all + ref.idx_off;
 #include "lm_problem.inc"
+}
+
+// One evaluation and one step -- test hook (mp_debug_lm_system): the setup of the kernels
+// above (lm_setup.inc), lm_evaluate at the start model into sh.red[0] and lm_step with the
+// job's radius, as the first pass of lm_problem.inc's loop runs them; sys[job] = the
+// reduced system in the full layout (entries past the variant's NA are zero), the active
+// mask and the step.  status as above; sys[job].pd = -1 with everything else zero where
+// the setup leaves nothing to do.
+template <int V>
+__global__ void __launch_bounds__(kLmBlock) lm_system_kernel(PairData D, PairConst C, const LmJob *jobs,
+                                                            const int *idx, const double *radius, LmSystem *sys,
+                                                            int *status) {
+#include "lm_setup.inc"
+    if (t0) {
+        LmSystem &o = sys[blockIdx.x];
+        o.cost = 0.0;
+        for (int q = 0; q < kLNFull * (kLNFull + 1) / 2; ++q) o.H[q] = 0.0;
+        for (int a = 0; a < kLNFull; ++a) {
+            o.g[a] = o.d[a] = 0.0;
+            o.col[a] = sh.col[a] >= 0 ? 1 : 0;
+        }
+        o.pd = -1;
+    }
+    if (sh.action == 0) return;
+    bool act[NA];
+#pragma unroll
+    for (int a = 0; a < NA; ++a) act[a] = sh.col[a] >= 0;
+    lm_evaluate<V, NA>(D, C, J, idx, sh.x, sh, sh.red[0]);
+    if (t0) {
+        LmSystem &o = sys[blockIdx.x];
+        const double *R = sh.red[0];
+        double d[NA];
+        const bool ok = lm_step<NA>(R, act, radius[blockIdx.x], d);
+        o.cost = R[kPack + NA];
+        for (int a = 0; a < NA; ++a) {
+            o.g[a] = R[kPack + a];
+            for (int b = a; b < NA; ++b) o.H[lm_up(a, b, kLNFull)] = R[lm_up(a, b, NA)];
+            o.d[a] = ok ? d[a] : 0.0;
+        }
+        o.pd = ok ? 1 : 0;
+    }
 }
 
 } // namespace
