@@ -829,6 +829,76 @@ int mp_debug_draw_weights_host(int64_t n, const void *weights, int32_t dtype, ui
                                int32_t *positive);
 int mp_debug_draw_weighted_host(int variant, int64_t n, const uint32_t *cum /* n + 1 */, uint64_t seed,
                                 int32_t point_share, int32_t pair, int32_t s, int32_t *out /* 10 */);
+/* The weighted stopping rule: the adaptive modes stop a weighted pair on the weight mass of its
+ * best model's inlier lists instead of their count ratios.  Every entry here is additive; the
+ * entries above, mp_ransac_weighted_set included, and their bytes are unchanged.
+ *
+ * The rule, for pair p of n correspondences and a handle: q_i = c[i + 1] - c[i] from the handle's
+ * table of that pair and W = c[n] < 2^32.  For a model m of the pair, L_t(m), t = 0..2, are the
+ * three inlier lists mp_select_set returns for the single candidate m (err_t < thr_t on the
+ * ungated errors).  If the handle reports the pair as weighted: mass[t] = sum of q_i over L_t as
+ * uint32 (distinct rows, so mass[t] <= W) and total = W.  If not (it was given no weights, or it
+ * fell back to the uniform draw): mass[t] = |L_t| and total = n.  count[t] = |L_t| in both cases.
+ * The weighted rule is the termination rule above with r[t] = (double)mass[t] / (double)total, and
+ * 0 when total = 0 or there is no winner; the exponents, the three bounds, ceil(log(1 - sp) /
+ * log(p_bad) + 0.5), the clamp in double, max(min_num_iterations, .) and the stop test are
+ * unchanged (mp_debug_ransac_required_mass: req[0], req[1] on the host, no device; mass NULL: no
+ * winner; MP_EINVAL for a mass above total).  Consequences: a pair that is not weighted gets
+ * mass / total = c / n, the count rule's bits; if all q_i = q > 0, (q c) / (q n) and c / n are
+ * correctly rounded quotients of one rational with operands exact in double, the same bits, so
+ * equal weights reproduce the count rule's stop points and, with the identity above, the
+ * unweighted call byte for byte.  There is NO promise of "never later": a list made mostly of
+ * low-confidence rows has a mass ratio below its count ratio.  Sampling without replacement and
+ * the fill are ignored, as the count rule ignores them.
+ *
+ * mp_inlier_mass_set: one record per entry e = (pair pair_ids[e] (NULL: e), models[e] in user
+ * units) from one launch of one workgroup per entry: integer sums only, so the record does not
+ * depend on the reduction order.  A pair may occur in any number of entries (no list buffer of
+ * the set is written); at most 2^24 entries; a call leaves nothing a later call can see.
+ * MP_EINVAL: a null set, a handle that is NULL, of another set or whose set was destroyed, a
+ * negative or too large num_entries, a pair outside the set, num_entries above num_pairs with
+ * pair_ids NULL.  A model with a NaN entry has empty lists (mass and count 0).
+ *
+ * mp_ransac_weighted_stop_set: mp_ransac_weighted_set with the weighted rule.  It needs step >= 1
+ * (MP_EINVAL) and a live handle of this set; otherwise it runs the chosen body's own checks and
+ * returns that body's own MP_EINVALs.  At every checkpoint, after the tracks are updated and
+ * before the rule is read, ONE launch computes the records of the still-active entries of weighted
+ * pairs whose rule model -- the minimal best with lo_rounds 0, the overall best at the
+ * checkpoint's end otherwise -- was replaced during that checkpoint.  Its counts must equal the
+ * track's: a mismatch is an internal error (MP_EDEVICE, the message names the pair), never a silent stop or
+ * continuation.
+ * Entries of pairs that are not weighted read their counts.  rule_mass[j] (nullable): what the
+ * rule last read for entry j, all zero with total = W or n when the entry never had a winner.
+ * Unchanged: stopped, num_samples, the minimal track, the final rounds, the units, pair_ids
+ * subsets (the table goes by the pair's index in the set), sample_chunk / model_chunk, and the
+ * bound that nothing grows with budget x pairs.  Entry j still equals, byte for byte, the
+ * fixed-budget identity of the body chosen at budget = results[j].num_samples.
+ *
+ * mp_debug_inlier_mass_host (no device): mass[0 .. 2] of three strictly ascending lists
+ * idx[offsets[t] .. offsets[t + 1]) (offsets[0] = 0, indices in 0 .. n - 1) under the table
+ * cum[0 .. n], n <= MP_DRAW_WEIGHT_MAX_N.  mp_debug_inlier_mass_stats: the launches of the mass
+ * stage since the last reset and their summed host milliseconds, upload to synchronise (each
+ * output nullable; reset != 0 clears both after reading). */
+typedef struct mp_inlier_mass {
+    uint32_t mass[3], total;
+    int32_t count[3], weighted;
+} mp_inlier_mass; /* 32 bytes */
+int mp_inlier_mass_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_entries,
+                       const int32_t *pair_ids /* nullable: pair e */, const mp_model *models /* num_entries */,
+                       mp_inlier_mass *out /* num_entries */);
+int mp_ransac_weighted_stop_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_sel,
+                                const int32_t *pair_ids, int32_t budget, int32_t step /* >= 1 */, uint64_t seed,
+                                int32_t point_share, int32_t rounds, int32_t lo_rounds /* 0: none */,
+                                int32_t lo_steps /* 0: none */, mp_model *models /* num_sel */,
+                                mp_ransac_result *results /* num_sel */, int32_t *inlier_idx /* nullable */,
+                                int32_t *stopped /* num_sel, nullable */, mp_ransac_lo_info *lo_info,
+                                mp_ransac_lo_steps_info *steps_info, int64_t sample_chunk, int64_t model_chunk,
+                                mp_inlier_mass *rule_mass /* num_sel, nullable */);
+int mp_debug_ransac_required_mass(int variant, uint32_t total, const uint32_t mass[3] /* nullable: no winner */,
+                                  const mp_ransac_options *options, uint32_t req[2]);
+int mp_debug_inlier_mass_host(int64_t n, const uint32_t *cum /* n + 1 */, const int64_t offsets[4],
+                              const int32_t *idx, uint32_t mass[3]);
+int mp_debug_inlier_mass_stats(int64_t *launches /* nullable */, double *ms /* nullable */, int32_t reset);
 /* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
  * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
  * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the

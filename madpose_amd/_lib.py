@@ -218,10 +218,20 @@ class mp_ransac_lo_steps_info(ctypes.Structure):
     ]
 
 
+class mp_inlier_mass(ctypes.Structure):
+    _fields_ = [
+        ("mass", ctypes.c_uint32 * 3),
+        ("total", ctypes.c_uint32),
+        ("count", ctypes.c_int32 * 3),
+        ("weighted", ctypes.c_int32),
+    ]
+
+
 # the weighted draw: the largest pair that may be given weights, the table entries (n + 1) the
 # device sampler reads through LDS (MP_DRAW_WEIGHT_MAX_N, MP_DRAW_STAGE_ENTRIES)
 DRAW_WEIGHT_MAX_N, DRAW_STAGE_ENTRIES = 65535, 4096
 LSQ_RULES = {"lsq": 0, "nonmin": 1}
+INLIER_MASS_MAX_ENTRIES = 1 << 24  # mp_inlier_mass_set's entries per call
 LO_STEPS_MAX = 64
 
 EXPORTS = {
@@ -313,6 +323,21 @@ EXPORTS = {
                                               c_int32_p, ctypes.POINTER(mp_ransac_lo_info),
                                               ctypes.POINTER(mp_ransac_lo_steps_info), ctypes.c_int64,
                                               ctypes.c_int64]),
+    "mp_inlier_mass_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, c_int32_p,
+                                          ctypes.POINTER(mp_model), ctypes.POINTER(mp_inlier_mass)]),
+    "mp_ransac_weighted_stop_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, c_int32_p,
+                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32,
+                                                   ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                   ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result),
+                                                   c_int32_p, c_int32_p, ctypes.POINTER(mp_ransac_lo_info),
+                                                   ctypes.POINTER(mp_ransac_lo_steps_info), ctypes.c_int64,
+                                                   ctypes.c_int64, ctypes.POINTER(mp_inlier_mass)]),
+    "mp_debug_ransac_required_mass": (ctypes.c_int, [ctypes.c_int, ctypes.c_uint32, ctypes.POINTER(ctypes.c_uint32),
+                                                     ctypes.POINTER(mp_ransac_options),
+                                                     ctypes.POINTER(ctypes.c_uint32)]),
+    "mp_debug_inlier_mass_host": (ctypes.c_int, [ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32), c_int64_p, c_int32_p,
+                                                 ctypes.POINTER(ctypes.c_uint32)]),
+    "mp_debug_inlier_mass_stats": (ctypes.c_int, [c_int64_p, c_double_p, ctypes.c_int32]),
     "mp_debug_draw_weights_host": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
                                                   ctypes.POINTER(ctypes.c_uint32), c_int32_p]),
     "mp_debug_draw_weighted_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32),

@@ -1583,6 +1583,42 @@ class PairSet:
             out.append(r)
         return out
 
+    def inlier_mass(self, models, weights, pair_ids=None):
+        """The weight mass of models' inlier lists (mp_inlier_mass_set): one InlierMass per
+        entry.  One entry per model; pair_ids (None: all pairs in order) MAY repeat a pair.
+        weights: draw_weights' object.  For entry (pair p, model m), with L_t the three lists
+        select([[m]], pair_ids=[p]) returns: count = their lengths; for a weighted pair mass[t] =
+        the sum over L_t of the quantised weights q_i and total = weights.total[p]; for a pair
+        that is not weighted mass = count and total = the pair's size.  weighted: which of the
+        two.  These are the numbers ransac(weighted_stop=True) divides.  One launch; integer
+        sums, so the values do not depend on the device's reduction order."""
+        h = self._live()
+        wh = self._weights_handle(weights)
+        P = len(self._sizes)
+        ne = len(models)
+        if pair_ids is None:
+            if ne != P:
+                raise ValueError(f"one model per pair: {ne} for {P} pairs")
+            ptr = None
+        else:
+            ids = np.ascontiguousarray(np.asarray(pair_ids, dtype=np.int64).reshape(-1))
+            if len(ids) != ne:
+                raise ValueError(f"one model per entry: {ne} for {len(ids)} pair_ids")
+            for j, k in enumerate(ids.tolist()):
+                if not 0 <= k < P:
+                    raise ValueError(f"pair_ids[{j}] = {k} is outside the set of {P} pairs")
+            ids = ids.astype(np.int32)
+            ptr = ids.ctypes.data_as(L.c_int32_p)
+        if ne > L.INLIER_MASS_MAX_ENTRIES:
+            raise ValueError("at most 2^24 entries per call")
+        if ne == 0:
+            return []
+        arr = (L.mp_model * ne)(*[_model_to_c(m, self.variant) for m in models])
+        res = (L.mp_inlier_mass * ne)()
+        L.check(L.lib().mp_inlier_mass_set(h, wh, ne, ptr, arr, res))
+        return [InlierMass(tuple(int(v) for v in q.mass), int(q.total), tuple(int(v) for v in q.count),
+                           bool(q.weighted)) for q in res]
+
     def _check_draw(self, budget, seed, point_share, ns):
         if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) or budget < 0:
             raise ValueError("budget must be a non-negative integer")
@@ -1610,8 +1646,9 @@ class PairSet:
         instead of uniformly; the sample types, the counter and the key are draw's, and equal
         weights give draw's bytes.  A pair with fewer positive weights than its largest sample
         draws uniformly (.weighted is False for it); a pair given weights may have at most
-        65535 correspondences.  The adaptive modes' termination rule still reads inlier count
-        ratios, which under informative weights is conservative.  ValueError, before any
+        65535 correspondences.  The adaptive modes' termination rule reads inlier count ratios
+        unless ransac is given weighted_stop=True, which makes it read the weights' mass over the
+        inlier lists (inlier_mass) divided by .total.  ValueError, before any
         library call, for a wrong length, dtype or contiguity and for a bad value in a host
         array."""
         h = self._live()
@@ -1748,7 +1785,7 @@ class PairSet:
                  slot[moffs[j]:moffs[j + 1]].copy()) for j in range(ns)]
 
     def ransac(self, budget=None, seed=0, point_share=None, samples=None, rounds=3, pair_ids=None, sample_chunk=0,
-               model_chunk=0, step=None, lo=None, lo_steps=None, weights=None):
+               model_chunk=0, step=None, lo=None, lo_steps=None, weights=None, weighted_stop=False):
         """Fixed-budget RANSAC on the selected pairs in one call (mp_ransac_set): draw ->
         hypothesize -> select -> refine on the device-resident pairs.  Exactly one of budget
         (samples drawn on the device as draw(budget, seed, point_share) draws them) and samples
@@ -1794,9 +1831,30 @@ class PairSet:
 
         weights (None, or draw_weights' object; needs budget, refuses samples): the drawn samples
         are draw(..., weights=weights)'s in every mode (mp_ransac_weighted_set), and each mode's
-        identity above holds with weights passed to both sides.  The termination rule is
-        unchanged: it reads inlier count ratios, so under informative weights it is conservative
-        and never stops a pair earlier than it does without weights."""
+        identity above holds with weights passed to both sides.  Without weighted_stop the
+        termination rule still reads inlier count ratios c[t] / n.
+
+        weighted_stop (a bool; True needs weights and step): the adaptive modes stop a weighted
+        pair on the weight mass of its rule model's inlier lists (mp_ransac_weighted_stop_set):
+        the rule's ratios are mass[t] / total, mass[t] the sum of the quantised weights q_i over
+        list t and total their sum over the pair (inlier_mass gives both for any model).  The
+        rule model is the best minimal model with step alone and the overall best at a
+        checkpoint's end with lo / lo_steps; its masses are computed by one launch per
+        checkpoint over the pairs whose rule model was replaced.  A pair that is not weighted
+        (w.weighted False) keeps the count rule, and equal weights give the count rule's stop
+        points bit for bit, so the bytes of the call with weighted_stop=False.  The mass rule is
+        NOT "never later" than the count rule: a list made mostly of low-confidence rows has a
+        mass ratio below its count ratio and stops later; informative weights, where inliers
+        carry the confidence, stop much earlier.  Each mode's identity above still holds at
+        r.num_samples.  r.rule_mass (a tuple of 3) and r.rule_total: what the rule last read
+        for the pair (zeros and the pair's total when it never had a winner); None and 0 with
+        weighted_stop off."""
+        if not isinstance(weighted_stop, (bool, np.bool_)):
+            raise ValueError("weighted_stop must be a bool")
+        if weighted_stop and weights is None:
+            raise ValueError("weighted_stop needs weights: the rule reads their mass over the inlier lists")
+        if weighted_stop and step is None:
+            raise ValueError("weighted_stop needs step: the rule is read at the adaptive mode's checkpoints")
         h = self._live()
         if self._hyp_error:
             raise ValueError(self._hyp_error.replace("hypothesize", "ransac"))
@@ -1854,8 +1912,20 @@ class PairSet:
         res = (L.mp_ransac_result * ns)()
         idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
         stopped = np.zeros(ns, dtype=np.int32)
-        info = sinfo = None
-        if wh is not None:
+        info = sinfo = rmass = None
+        if wh is not None and weighted_stop:
+            if lo is not None:
+                info = (L.mp_ransac_lo_info * ns)()
+            if lo_steps is not None:
+                sinfo = (L.mp_ransac_lo_steps_info * ns)()
+            rmass = (L.mp_inlier_mass * ns)()
+            L.check(L.lib().mp_ransac_weighted_stop_set(h, wh, ns, ptr, budget, int(step), seed, share, int(rounds),
+                                                        0 if lo is None else int(lo),
+                                                        0 if lo_steps is None else int(lo_steps), arr, res,
+                                                        idx.ctypes.data_as(L.c_int32_p),
+                                                        stopped.ctypes.data_as(L.c_int32_p), info, sinfo,
+                                                        int(sample_chunk), int(model_chunk), rmass))
+        elif wh is not None:
             if lo is not None:
                 info = (L.mp_ransac_lo_info * ns)()
             if lo_steps is not None:
@@ -1893,6 +1963,8 @@ class PairSet:
             r = RansacResult()
             r.num_samples, r.num_candidates = int(q.num_samples), int(q.num_candidates)
             r.stopped = bool(stopped[j])
+            if rmass is not None:
+                r.rule_mass, r.rule_total = tuple(int(v) for v in rmass[j].mass), int(rmass[j].total)
             if info is not None:
                 r.lo_runs, r.lo_accepted, r.lo_index = (int(info[j].lo_runs), int(info[j].lo_accepted),
                                                         int(info[j].lo_index))
@@ -1961,6 +2033,18 @@ class DrawWeights:
         return self._h
 
 
+class InlierMass:
+    """One entry's outcome of PairSet.inlier_mass: mass (three ints, the weight mass of the
+    model's three inlier lists), total (the pair's weight total, or its size when the pair is
+    not weighted), count (the lists' lengths) and weighted."""
+
+    def __init__(self, mass=(0, 0, 0), total=0, count=(0, 0, 0), weighted=False):
+        self.mass, self.total, self.count, self.weighted = mass, total, count, weighted
+
+    def __repr__(self):
+        return f"InlierMass(mass={self.mass} of {self.total}, count={self.count}, weighted={self.weighted})"
+
+
 class LsqFitResult:
     """One entry's outcome of PairSet.lsq_fit: score and num_inliers (of the given model),
     num_wide, subset_sizes, status (3: skipped; else the LM's: 1 refined), model and model_row
@@ -1996,7 +2080,9 @@ class RansacResult:
     whose local optimisation gave the returned start model; 0, 0 and -1 otherwise); lo_step,
     lo_stage, lo_step_offers, lo_step_accepted (ransac(lo_steps=...) only: the LO step and stage
     that produced the returned start model, -1 when no step did, and the steps' offers to the
-    overall best and those accepted; -1, -1, 0 and 0 otherwise)."""
+    overall best and those accepted; -1, -1, 0 and 0 otherwise); rule_mass, rule_total
+    (ransac(weighted_stop=True) only: the three weight masses and the total the termination rule
+    last read for the pair; None and 0 otherwise)."""
 
     def __init__(self):
         self.num_samples = self.num_candidates = 0
@@ -2005,6 +2091,7 @@ class RansacResult:
         self.lo_index = -1
         self.lo_step = self.lo_stage = -1
         self.lo_step_offers = self.lo_step_accepted = 0
+        self.rule_mass, self.rule_total = None, 0
         self.index = self.sample = self.slot = self.solver_type = -1
         self.score_selected = self.score_initial = self.score_final = float(np.finfo(np.float64).max)
         self.rounds_run = self.rounds_accepted = 0

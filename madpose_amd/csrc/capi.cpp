@@ -608,6 +608,75 @@ int mp_ransac_weighted_set(mp_pair_set *set, const mp_draw_weights *handle, int3
     });
 }
 
+int mp_inlier_mass_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_entries, const int32_t *pair_ids,
+                       const mp_model *models, mp_inlier_mass *out) {
+    return guarded([&]() {
+        static_assert(sizeof(mp::InlierMass) == sizeof(mp_inlier_mass) && sizeof(mp_inlier_mass) == 32,
+                      "inlier mass layout");
+        if (!set) throw std::invalid_argument("null pair set");
+        if (!handle) throw std::invalid_argument("null draw weights");
+        mp::inlier_mass_set(reinterpret_cast<mp::PairSet *>(set), reinterpret_cast<const mp::DrawWeights *>(handle),
+                            num_entries, pair_ids, reinterpret_cast<const mp::Model *>(models),
+                            reinterpret_cast<mp::InlierMass *>(out));
+        return MP_OK;
+    });
+}
+
+int mp_ransac_weighted_stop_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_sel,
+                                const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
+                                int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
+                                mp_model *models, mp_ransac_result *results, int32_t *inlier_idx, int32_t *stopped,
+                                mp_ransac_lo_info *lo_info, mp_ransac_lo_steps_info *steps_info, int64_t sample_chunk,
+                                int64_t model_chunk, mp_inlier_mass *rule_mass) {
+    return guarded([&]() {
+        if (!set) throw std::invalid_argument("null pair set");
+        if (!handle) throw std::invalid_argument("null draw weights");
+        mp::PairSet *S = reinterpret_cast<mp::PairSet *>(set);
+        const mp::DrawWeights *W = reinterpret_cast<const mp::DrawWeights *>(handle);
+        mp::Model *M = reinterpret_cast<mp::Model *>(models);
+        mp::RansacResult *Q = reinterpret_cast<mp::RansacResult *>(results);
+        mp::RansacLoInfo *LI = reinterpret_cast<mp::RansacLoInfo *>(lo_info);
+        mp::InlierMass *RM = reinterpret_cast<mp::InlierMass *>(rule_mass);
+        if (step < 1) throw std::invalid_argument("the weighted stop needs step >= 1: the rule is read at checkpoints");
+        if (lo_rounds == 0 && lo_steps != 0) throw std::invalid_argument("lo_steps needs lo_rounds");
+        if (lo_rounds == 0)
+            mp::ransac_adaptive_set(S, num_sel, pair_ids, budget, step, seed, point_share, rounds, M, Q, inlier_idx,
+                                    stopped, sample_chunk, model_chunk, W, true, RM);
+        else if (lo_steps == 0)
+            mp::ransac_lo_set(S, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, M, Q, inlier_idx,
+                              stopped, LI, sample_chunk, model_chunk, W, true, RM);
+        else
+            mp::ransac_lo_steps_set(S, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, lo_steps, M,
+                                    Q, inlier_idx, stopped, LI, reinterpret_cast<mp::RansacLoStepsInfo *>(steps_info),
+                                    sample_chunk, model_chunk, W, true, RM);
+        return MP_OK;
+    });
+}
+
+int mp_debug_ransac_required_mass(int variant, uint32_t total, const uint32_t mass[3], const mp_ransac_options *options,
+                                  uint32_t req[2]) {
+    return guarded([&]() {
+        if (!options) throw std::invalid_argument("null options");
+        mp::ransac_required_mass(variant, total, mass, to_opts(options), req);
+        return MP_OK;
+    });
+}
+
+int mp_debug_inlier_mass_host(int64_t n, const uint32_t *cum, const int64_t offsets[4], const int32_t *idx,
+                              uint32_t mass[3]) {
+    return guarded([&]() {
+        mp::inlier_mass_host_hook(n, cum, offsets, idx, mass);
+        return MP_OK;
+    });
+}
+
+int mp_debug_inlier_mass_stats(int64_t *launches, double *ms, int32_t reset) {
+    return guarded([&]() {
+        mp::inlier_mass_stats(launches, ms, reset != 0);
+        return MP_OK;
+    });
+}
+
 int mp_debug_draw_weights_host(int64_t n, const void *weights, int32_t dtype, uint32_t *cum, int32_t *positive) {
     return guarded([&]() {
         mp::draw_weights_host(n, weights, dtype, cum, positive);

@@ -4452,7 +4452,212 @@ void refine_winners(PairSet *set, hipStream_t stream, const PairSel sel, int32_t
         for (int t = 0; t < 3; ++t) Q.num_inliers[t] = F.num_inliers[t];
     }
 }
+
+// mass_run's device arrays, grown to the largest run seen: the adaptive bodies size them once
+// for their selection, so nothing grows with the rounds
+struct MassBuffers {
+    size_t cap = 0;
+    std::unique_ptr<DevArray<unsigned char>> d_in; // cap ScoreRec, then cap MassItem: one upload
+    std::unique_ptr<DevArray<MassOut>> d_out;
+    std::vector<unsigned char> h_in;
+    void ensure(size_t n) {
+        if (n <= cap) return;
+        d_in.reset();
+        d_out.reset();
+        d_in.reset(new DevArray<unsigned char>(n * (sizeof(ScoreRec) + sizeof(MassItem))));
+        d_out.reset(new DevArray<MassOut>(n));
+        cap = n;
+    }
+};
+
+std::mutex g_mass_mu;
+int64_t g_mass_launches = 0;
+double g_mass_ms = 0.0;
+
+// The weight mass of the inlier lists of given models (kernels/inlier_mass.h; the body of
+// mp_inlier_mass_set and the weighted rule's stage).  Entry e is the model models[e] (user units)
+// of pair pairs[e]; it goes to problem units and to a ScoreRec by the path of refine_run and of
+// select_run's winner sweep, so the lists are the ones select returns for that single model.
+// weighted[e] != 0: the rows weigh the q_i of the pair's table in w; 0: 1 each, total = n.  One
+// upload, one launch, one copy back and one synchronise per run; it reads the set and the
+// tables and writes only out (no list buffer of the set is touched, so a pair may repeat).
+void mass_run(ResidentPairs &R, hipStream_t stream, const DrawWeights *w, size_t m, const int32_t *pairs,
+              const unsigned char *weighted, const Model *models, MassOut *out, MassBuffers &B) {
+    if (m == 0) return;
+    static_assert(sizeof(ScoreRec) % alignof(MassItem) == 0 && sizeof(MassOut) == 32, "mass_run's packing");
+    const auto t0 = Clock::now();
+    const int variant = R.variant;
+    B.ensure(m);
+    B.h_in.resize(m * (sizeof(ScoreRec) + sizeof(MassItem)));
+    ScoreRec *recs = reinterpret_cast<ScoreRec *>(B.h_in.data());
+    MassItem *items = reinterpret_cast<MassItem *>(B.h_in.data() + m * sizeof(ScoreRec));
+    bool any = false;
+    for (size_t e = 0; e < m; ++e) {
+        const int k = pairs[e];
+        Model c = models[e];
+        if (variant == kSF || variant == kTF) {
+            c.focal0 /= R.norm_scale[(size_t)k];
+            c.focal1 /= R.norm_scale[(size_t)k];
+        }
+        prepare_score_rec(R.Ch[(size_t)k], c, recs[e]);
+        items[e].pair = k;
+        items[e].weighted = weighted[e] ? 1 : 0;
+        any = any || weighted[e];
+    }
+    if (any && (!w || !w->d_cum)) throw std::logic_error("mass_run: a weighted entry without a table");
+    const unsigned char *d_in = B.d_in->p;
+    MP_HIP(hipMemcpyAsync(B.d_in->p, B.h_in.data(), B.h_in.size(), hipMemcpyHostToDevice, stream));
+    MP_HIP(launch_inlier_mass(stream, R.v, R.d_D.p, R.d_C.p, reinterpret_cast<const MassItem *>(d_in + m * sizeof(ScoreRec)),
+                              reinterpret_cast<const ScoreRec *>(d_in), (int)m, any ? w->d_cum->p : nullptr,
+                              any ? w->d_cum_off->p : nullptr, B.d_out->p));
+    MP_HIP(hipMemcpyAsync(out, B.d_out->p, sizeof(MassOut) * m, hipMemcpyDeviceToHost, stream));
+    MP_HIP(hipStreamSynchronize(stream));
+    std::lock_guard<std::mutex> lk(g_mass_mu);
+    ++g_mass_launches;
+    g_mass_ms += 1e3 * secs(t0);
+}
+
+// The weighted rule's per-entry state of the adaptive bodies (weighted_stop): what the rule
+// last read.  For an entry of a weighted pair the masses of its rule model's lists, replaced
+// exactly when the rule model is; for any other entry its counts over n.
+struct RuleMass {
+    std::vector<InlierMass> rm;      // per entry
+    std::vector<unsigned char> dirty; // the rule model changed during this checkpoint
+    MassBuffers bufs;
+    std::vector<int32_t> pairs;
+    std::vector<unsigned char> flags;
+    std::vector<Model> ms;
+    std::vector<MassOut> outs;
+    std::vector<int> which;
+    void init(const ResidentPairs &R, const PairSel sel, const DrawWeights *w) {
+        rm.assign((size_t)sel.n, InlierMass{});
+        dirty.assign((size_t)sel.n, 0);
+        for (int j = 0; j < sel.n; ++j) {
+            const int k = sel[j];
+            rm[(size_t)j].weighted = w->weighted[(size_t)k];
+            rm[(size_t)j].total = w->weighted[(size_t)k] ? w->total[(size_t)k] : (uint32_t)R.n[(size_t)k];
+        }
+        bufs.ensure((size_t)sel.n);
+    }
+    // One mass_run over the active entries of weighted pairs whose rule model changed; counts_of(j):
+    // the track's counts of entry j's rule model, which the kernel's must equal.
+    template <class F>
+    void update(ResidentPairs &R, hipStream_t stream, const DrawWeights *w, const PairSel sel,
+                const std::vector<int> &active, const Model *models, F counts_of) {
+        which.clear(), pairs.clear(), flags.clear(), ms.clear();
+        for (int j : active) {
+            if (!dirty[(size_t)j]) continue;
+            dirty[(size_t)j] = 0;
+            InlierMass &M = rm[(size_t)j];
+            const int32_t *c = counts_of(j);
+            if (!M.weighted) { // (not weighted: the counts, as the count rule reads them)
+                for (int t = 0; t < 3; ++t) M.mass[t] = (uint32_t)c[t], M.count[t] = c[t];
+                continue;
+            }
+            which.push_back(j);
+            pairs.push_back(sel[j]);
+            flags.push_back(1);
+            ms.push_back(models[j]);
+        }
+        if (which.empty()) return;
+        outs.resize(which.size());
+        mass_run(R, stream, w, which.size(), pairs.data(), flags.data(), ms.data(), outs.data(), bufs);
+        for (size_t i = 0; i < which.size(); ++i) {
+            const int j = which[i];
+            InlierMass &M = rm[(size_t)j];
+            const MassOut &O = outs[i];
+            const int32_t *c = counts_of(j);
+            if (O.count[0] != c[0] || O.count[1] != c[1] || O.count[2] != c[2] || O.total != M.total)
+                throw std::logic_error("weighted stop: the mass stage's counts of pair " + std::to_string(sel[j]) +
+                                       " differ from its track's");
+            for (int t = 0; t < 3; ++t) {
+                if (O.mass[t] > O.total)
+                    throw std::logic_error("weighted stop: a mass above the total, pair " + std::to_string(sel[j]));
+                M.mass[t] = O.mass[t], M.count[t] = O.count[t];
+            }
+        }
+    }
+    // req[0 .. 1] of entry j: the weighted rule on its masses, or the count rule on its counts
+    void required(int j, int kmd, int kpt, int64_t n, bool winner, const int32_t *counts, const StopOptions &so,
+                  uint32_t req[2]) const {
+        const InlierMass &M = rm[(size_t)j];
+        for (int s = 0; s < 2; ++s)
+            req[s] = M.weighted ? required_samples_mass(s, kmd, kpt, M.total, winner ? M.mass : nullptr, so)
+                                : required_samples(s, kmd, kpt, n, winner ? counts : nullptr, so);
+    }
+};
 } // namespace
+
+void inlier_mass_stats(int64_t *launches, double *ms, bool reset) {
+    std::lock_guard<std::mutex> lk(g_mass_mu);
+    if (launches) *launches = g_mass_launches;
+    if (ms) *ms = g_mass_ms;
+    if (reset) g_mass_launches = 0, g_mass_ms = 0.0;
+}
+
+void inlier_mass_set(PairSet *set, const DrawWeights *weights, int32_t num_entries, const int32_t *pair_ids,
+                     const Model *models, InlierMass *out) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (num_entries < 0 || num_entries > kMassEntriesMax) throw std::invalid_argument("num_entries must be in 0..2^24");
+    std::lock_guard<std::mutex> lk(set->mu);
+    check_draw_weights(set, weights);
+    if (!pair_ids && num_entries > set->num_pairs) throw std::invalid_argument("more entries than pairs without pair_ids");
+    for (int32_t e = 0; pair_ids && e < num_entries; ++e)
+        if (pair_ids[e] < 0 || pair_ids[e] >= set->num_pairs)
+            throw std::invalid_argument("pair_ids[" + std::to_string(e) + "] is outside the set");
+    if (num_entries == 0) return;
+    if (!models || !out) throw std::invalid_argument("null models or output");
+    ResidentPairs &R = *set->R;
+    std::vector<int32_t> pairs((size_t)num_entries);
+    std::vector<unsigned char> flags((size_t)num_entries);
+    for (int32_t e = 0; e < num_entries; ++e) {
+        pairs[(size_t)e] = pair_ids ? pair_ids[e] : e;
+        flags[(size_t)e] = weights->weighted[(size_t)pairs[(size_t)e]] ? 1 : 0;
+    }
+    std::vector<MassOut> outs((size_t)num_entries);
+    CtxLease lease(set->device);
+    MassBuffers B;
+    mass_run(R, lease.c->stream, weights, (size_t)num_entries, pairs.data(), flags.data(), models, outs.data(), B);
+    for (int32_t e = 0; e < num_entries; ++e) {
+        const MassOut &O = outs[(size_t)e];
+        const int k = pairs[(size_t)e];
+        const uint32_t total = flags[(size_t)e] ? weights->total[(size_t)k] : (uint32_t)R.n[(size_t)k];
+        if (O.total != total) throw std::logic_error("inlier_mass: the table's total of pair " + std::to_string(k) + " differs from the handle's");
+        InlierMass &M = out[e];
+        for (int t = 0; t < 3; ++t) M.mass[t] = O.mass[t], M.count[t] = O.count[t];
+        M.total = O.total;
+        M.weighted = flags[(size_t)e];
+    }
+}
+
+void ransac_required_mass(int variant, uint32_t total, const uint32_t *mass, const RansacOptions &opts, uint32_t *req) {
+    if (variant < 0 || variant > 2) throw std::invalid_argument("variant must be 0, 1 or 2");
+    if (!req) throw std::invalid_argument("null output");
+    for (int t = 0; mass && t < 3; ++t)
+        if (mass[t] > total) throw std::invalid_argument("mass must be in 0..total");
+    const StopOptions so{opts.success_probability, opts.min_num_iterations, opts.max_num_iterations_per_solver};
+    for (int s = 0; s < 2; ++s) req[s] = required_samples_mass(s, draw_k_md(variant), draw_k_pt(variant), total, mass, so);
+}
+
+void inlier_mass_host_hook(int64_t n, const uint32_t *cum, const int64_t *offsets, const int32_t *idx, uint32_t *mass) {
+    if (n < 0 || n > kDrawWeightMaxN) throw std::invalid_argument("n must be in 0..65535");
+    if (!cum || !offsets || !mass) throw std::invalid_argument("null table, offsets or output");
+    if (cum[0] != 0) throw std::invalid_argument("cum[0] must be 0");
+    for (int64_t i = 0; i < n; ++i)
+        if (cum[i + 1] < cum[i] || cum[i + 1] - cum[i] > kDrawWeightQMax)
+            throw std::invalid_argument("cum must rise by at most 65535 per entry");
+    if (offsets[0] != 0) throw std::invalid_argument("offsets must start at 0");
+    for (int t = 0; t < 3; ++t)
+        if (offsets[t + 1] < offsets[t] || offsets[t + 1] - offsets[t] > n)
+            throw std::invalid_argument("a list must hold 0..n indices");
+    if (offsets[3] > 0 && !idx) throw std::invalid_argument("null idx");
+    for (int t = 0; t < 3; ++t)
+        for (int64_t j = offsets[t]; j < offsets[t + 1]; ++j) {
+            if (idx[j] < 0 || idx[j] >= n) throw std::invalid_argument("index outside 0 .. n - 1");
+            if (j > offsets[t] && idx[j] <= idx[j - 1]) throw std::invalid_argument("lists must ascend strictly");
+        }
+    inlier_mass_host(cum, offsets, idx, mass);
+}
 
 RansacTiming ransac_timing_last() {
     std::lock_guard<std::mutex> lk(g_ransac_mu);
@@ -4736,8 +4941,9 @@ void select_argmin_direct(int32_t num_pairs, const int64_t *model_offsets, const
 void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
                          int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk,
-                         const DrawWeights *weights) {
+                         const DrawWeights *weights, bool weighted_stop, InlierMass *rule_mass) {
     if (!set) throw std::invalid_argument("null pair set");
+    if (weighted_stop && !weights) throw std::invalid_argument("weighted_stop needs draw weights");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
     if (model_chunk < 0) throw std::invalid_argument("model_chunk must not be negative");
@@ -4781,6 +4987,8 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     }
     CtxLease lease(set->device);
     hipStream_t stream = lease.c->stream;
+    RuleMass rule; // (weighted_stop: what the rule reads, host/ransac_stop.h required_samples_mass)
+    if (weighted_stop) rule.init(R, sel, weights);
     if (!active.empty()) {
         // (the first round is the largest: its buffers serve every round)
         HypBuffers B(v, (int64_t)active.size() * std::min(step, budget), sample_chunk, true, true);
@@ -4840,13 +5048,25 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
                     Q.score_selected = Q.score_initial = Q.score_final = W.best_score;
                     for (int k = 0; k < 3; ++k) Q.num_inliers[k] = W.num_inliers[k];
                     models[j] = co.models[(size_t)(cp.moff[(size_t)a] + W.best_index)];
+                    if (weighted_stop) rule.dirty[(size_t)j] = 1;
                 }
                 Q.num_samples += count[(size_t)a];
                 Q.num_candidates += (int32_t)(cp.moff[(size_t)a + 1] - cp.moff[(size_t)a]);
+            }
+            // ---- weighted_stop: one mass_run over the entries whose running best was replaced ----
+            if (weighted_stop)
+                rule.update(R, stream, weights, sel, active, models, [&](int j) { return results[j].num_inliers; });
+            // ---- the rule, on the running best's counts (weighted_stop: its masses) ----
+            for (int a = 0; a < na; ++a) {
+                const int j = active[(size_t)a];
+                RansacResult &Q = results[j];
                 uint32_t req[2];
-                for (int s = 0; s < 2; ++s)
-                    req[s] = required_samples(s, kmd, kpt, R.n[sel[j]], Q.best_candidate >= 0 ? Q.num_inliers : nullptr,
-                                              so);
+                if (weighted_stop)
+                    rule.required(j, kmd, kpt, R.n[sel[j]], Q.best_candidate >= 0, Q.num_inliers, so, req);
+                else
+                    for (int s = 0; s < 2; ++s)
+                        req[s] = required_samples(s, kmd, kpt, R.n[sel[j]],
+                                                  Q.best_candidate >= 0 ? Q.num_inliers : nullptr, so);
                 if (stop_reached(req, &drawn[2 * (size_t)j])) {
                     if (stopped) stopped[j] = 1;
                 } else if (Q.num_samples < budget) {
@@ -4856,6 +5076,7 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
             active.swap(next);
         }
     }
+    if (weighted_stop && rule_mass) std::copy(rule.rm.begin(), rule.rm.end(), rule_mass);
     // ---- refine: once, the pairs with a winner ----
     refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
 }
@@ -4865,8 +5086,10 @@ namespace {
 void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk, int32_t lo_steps, RansacLoStepsInfo *steps_info, const DrawWeights *weights) {
+                   int64_t model_chunk, int32_t lo_steps, RansacLoStepsInfo *steps_info, const DrawWeights *weights,
+                   bool weighted_stop, InlierMass *rule_mass) {
     if (!set) throw std::invalid_argument("null pair set");
+    if (weighted_stop && !weights) throw std::invalid_argument("weighted_stop needs draw weights");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (lo_rounds < 1 || lo_rounds > 64) throw std::invalid_argument("lo_rounds must be in 1..64");
     if (num_sel > 0 && !lo_info) throw std::invalid_argument("null lo_info");
@@ -4916,6 +5139,8 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
     }
     CtxLease lease(set->device);
     hipStream_t stream = lease.c->stream;
+    RuleMass rule; // (weighted_stop: what the rule reads, host/ransac_stop.h required_samples_mass)
+    if (weighted_stop) rule.init(R, sel, weights);
     if (!active.empty()) {
         // (the first round is the largest: its buffers serve every round)
         HypBuffers B(v, (int64_t)active.size() * std::min(step, budget), sample_chunk, true, true);
@@ -5006,6 +5231,7 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                         lo_step_clear(strack[(size_t)j]);
                         models[j] = minimal[(size_t)j];
                         take_lists(j, W.num_inliers);
+                        if (weighted_stop) rule.dirty[(size_t)j] = 1;
                     }
                     lo_j.push_back(j);
                     lo_ids.push_back(sel[j]);
@@ -5030,6 +5256,7 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                         lo_step_clear(strack[(size_t)j]);
                         models[j] = lo_models[(size_t)i];
                         take_lists(j, F.num_inliers);
+                        if (weighted_stop) rule.dirty[(size_t)j] = 1;
                     }
                 }
                 // ---- the LO steps (host/ransac_lo_steps.h): every step of every such entry goes
@@ -5075,8 +5302,10 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                         for (size_t e = 0; e < m; ++e) {
                             const int j = lo_j[(size_t)st_i[e]];
                             if (lo_step_offer(track[(size_t)j], strack[(size_t)j], results[j].best_candidate, st_r[e],
-                                              q - 1, st_res[e].score, st_res[e].num_inliers))
+                                              q - 1, st_res[e].score, st_res[e].num_inliers)) {
                                 models[j] = st_in[e];
+                                if (weighted_stop) rule.dirty[(size_t)j] = 1;
+                            }
                         }
                     }
                     // the finals: one select over each entry's live steps' last models, in step order
@@ -5104,20 +5333,29 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                             const size_t e = (size_t)fin_first[(size_t)f] + (size_t)W.best_index;
                             const int j = lo_j[(size_t)st_i[e]];
                             if (lo_step_offer(track[(size_t)j], strack[(size_t)j], results[j].best_candidate, st_r[e],
-                                              2 + Q, W.best_score, W.num_inliers))
+                                              2 + Q, W.best_score, W.num_inliers)) {
                                 models[j] = st_m[e];
+                                if (weighted_stop) rule.dirty[(size_t)j] = 1;
+                            }
                         }
                     }
                 }
             }
-            // ---- the rule, on the overall best's counts ----
+            // ---- weighted_stop: one mass_run over the entries whose overall best was replaced
+            // during this checkpoint, on the overall best as it stands at its end ----
+            if (weighted_stop)
+                rule.update(R, stream, weights, sel, active, models, [&](int j) { return track[(size_t)j].counts; });
+            // ---- the rule, on the overall best's counts (weighted_stop: its masses) ----
             next.clear();
             for (int a = 0; a < na; ++a) {
                 const int j = active[(size_t)a];
                 const LoTrack &K = track[(size_t)j];
                 uint32_t req[2];
-                for (int s = 0; s < 2; ++s)
-                    req[s] = required_samples(s, kmd, kpt, R.n[sel[j]], K.source != 0 ? K.counts : nullptr, so);
+                if (weighted_stop)
+                    rule.required(j, kmd, kpt, R.n[sel[j]], K.source != 0, K.counts, so, req);
+                else
+                    for (int s = 0; s < 2; ++s)
+                        req[s] = required_samples(s, kmd, kpt, R.n[sel[j]], K.source != 0 ? K.counts : nullptr, so);
                 if (stop_reached(req, &drawn[2 * (size_t)j])) {
                     if (stopped) stopped[j] = 1;
                 } else if (results[j].num_samples < budget) {
@@ -5133,6 +5371,7 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
         if (K.source != 0) Q.score_initial = Q.score_final = K.score;
         for (int t = 0; t < 3; ++t) Q.num_inliers[t] = K.counts[t];
         lo_info[j] = RansacLoInfo{K.lo_runs, K.lo_accepted, K.lo_index, 0};
+        if (weighted_stop && rule_mass) rule_mass[j] = rule.rm[(size_t)j];
         if (steps_info) {
             const LoStepTrack &S = strack[(size_t)j];
             steps_info[j] = RansacLoStepsInfo{S.lo_step, S.lo_stage, S.offers, S.accepted};
@@ -5176,16 +5415,18 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
 void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk, const DrawWeights *weights) {
+                   int64_t model_chunk, const DrawWeights *weights, bool weighted_stop, InlierMass *rule_mass) {
     ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
-                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, 0, nullptr, weights);
+                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, 0, nullptr, weights, weighted_stop,
+                  rule_mass);
 }
 
 void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
                          Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
                          RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
-                         int64_t model_chunk, const DrawWeights *weights) {
+                         int64_t model_chunk, const DrawWeights *weights, bool weighted_stop,
+                         InlierMass *rule_mass) {
     if (!set) throw std::invalid_argument("null pair set");
     if (lo_steps < 1 || lo_steps > kLoStepsMax) throw std::invalid_argument("lo_steps must be in 1..64");
     if (num_sel > 0 && !steps_info) throw std::invalid_argument("null steps_info");
@@ -5194,7 +5435,8 @@ void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     if (!(set->opts.threshold_multiplier > 0.0) || !(set->opts.threshold_multiplier <= DBL_MAX))
         throw std::invalid_argument("threshold_multiplier must be positive and finite with lo_steps");
     ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
-                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, lo_steps, steps_info, weights);
+                  inlier_idx, stopped, lo_info, sample_chunk, model_chunk, lo_steps, steps_info, weights,
+                  weighted_stop, rule_mass);
 }
 
 void ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts, const int32_t *candidate,

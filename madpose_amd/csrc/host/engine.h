@@ -352,6 +352,43 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
                 int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
                 const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
                 int64_t sample_chunk, int64_t model_chunk, const DrawWeights *weights = nullptr);
+// The weight mass of models' inlier lists and the weighted stopping rule (mp_inlier_mass_set,
+// mp_ransac_weighted_stop_set; kernels/inlier_mass.h, host/ransac_stop.h required_samples_mass).
+// q_i = c[i + 1] - c[i] are the quantised confidences of the handle's table of the pair and
+// W = c[n] < 2^32 their sum.  For a model of a pair, L_t (t = 0..2) are the lists select
+// returns for that single candidate (err_t < thr_t, ungated errors).  A weighted pair:
+// mass[t] = the sum of q_i over L_t (uint32; distinct rows, so mass <= W) and total = W.  A
+// pair that is not weighted (no weights given, or fallen back): mass[t] = |L_t|, total = n.
+// count[t] = |L_t| always.
+// inlier_mass_set: entry e is the model models[e] (user units) of pair pair_ids[e] (null: e);
+// a pair MAY repeat, at most 2^24 entries; one upload, launch, copy and synchronise; nothing
+// of the set is written.
+// weighted_stop (the three adaptive entries below; needs weights): the termination rule of a
+// weighted pair reads r[t] = mass[t] / total of its rule model -- the running best of
+// ransac_adaptive_set, the overall best at the checkpoint's end of the lo bodies -- instead
+// of counts[t] / n.  At a checkpoint, after the tracks are updated and before the rule is
+// read, ONE mass run covers the still-active entries of weighted pairs whose rule model
+// was replaced during that checkpoint; its counts must equal the track's (std::logic_error
+// naming the pair otherwise).  Entries of pairs that are not weighted read their counts, the
+// count rule's bits.  rule_mass[j] (nullable): what the rule last read for entry j; all zero
+// with total = W or n for an entry that never had a winner.  Draws, walks, tracks, the final
+// rounds and the result layout are untouched; with weighted_stop off no launch or byte of the
+// call changes.  The device arrays of the stage are sized once for the selection.
+constexpr int32_t kMassEntriesMax = 1 << 24;
+struct InlierMass {
+    uint32_t mass[3], total;
+    int32_t count[3], weighted;
+};
+void inlier_mass_set(PairSet *set, const DrawWeights *weights, int32_t num_entries, const int32_t *pair_ids,
+                     const Model *models, InlierMass *out);
+// Test hooks, no device.  ransac_required_mass (mp_debug_ransac_required_mass): req[0], req[1] of
+// the weighted rule on (total, mass[0 .. 2]); mass null: no winner.  inlier_mass_host_hook
+// (mp_debug_inlier_mass_host): the masses of three strictly ascending lists under a table.
+// inlier_mass_stats (mp_debug_inlier_mass_stats): the mass runs since the last reset and their
+// summed host milliseconds (upload to synchronise).
+void ransac_required_mass(int variant, uint32_t total, const uint32_t *mass, const RansacOptions &opts, uint32_t *req);
+void inlier_mass_host_hook(int64_t n, const uint32_t *cum, const int64_t *offsets, const int32_t *idx, uint32_t *mass);
+void inlier_mass_stats(int64_t *launches, double *ms, bool reset);
 // ransac_adaptive_set (mp_ransac_adaptive_set): ransac_set's drawn mode with a per-pair
 // number of samples.  Samples go through draw -> hypothesize_run -> select_run in rounds of
 // `step` per still-active pair (checkpoints m_k = min(k step, budget)); select_run continues
@@ -365,7 +402,8 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
 void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
                          int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk,
-                         const DrawWeights *weights = nullptr);
+                         const DrawWeights *weights = nullptr, bool weighted_stop = false,
+                         InlierMass *rule_mass = nullptr);
 // ransac_lo_set (mp_ransac_lo_set): ransac_adaptive_set with the estimators' local
 // optimisation prefix inside the rounds, two tracks per pair.  The minimal track is
 // ransac_adaptive_set's in every bit (select_run is seeded with the minimal best's score).
@@ -391,7 +429,8 @@ struct RansacLoInfo {
 void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk, const DrawWeights *weights = nullptr);
+                   int64_t model_chunk, const DrawWeights *weights = nullptr, bool weighted_stop = false,
+                   InlierMass *rule_mass = nullptr);
 // ransac_lo_steps_set (mp_ransac_lo_steps_set): ransac_lo_set with the num_lo_steps steps of the
 // estimators' LocalOptimization after each local optimisation (host/ransac_lo_steps.h): lo_steps
 // steps per entry whose minimal best was replaced, from the model the relaxed refinement
@@ -407,7 +446,8 @@ void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
                          uint64_t seed, int32_t point_share, int32_t rounds, int32_t lo_rounds, int32_t lo_steps,
                          Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
                          RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
-                         int64_t model_chunk, const DrawWeights *weights = nullptr);
+                         int64_t model_chunk, const DrawWeights *weights = nullptr, bool weighted_stop = false,
+                         InlierMass *rule_mass = nullptr);
 // Test hook (mp_debug_ransac_lo_track; no device): host/ransac_lo_track.h walked over
 // num_rounds rounds in each of which the minimal best was replaced (its score and counts,
 // its candidate index, and its LO's rounds_accepted, score_final and counts).  score: the

@@ -47,6 +47,42 @@ inline uint32_t required_samples(int s, int k_md, int k_pt, int64_t n, const int
     return std::max(o.min_num_iterations, r);
 }
 
+// The weighted rule (mp_ransac_weighted_stop_set): required_samples with r[t] = mass[t] / total,
+// mass[t] the sum of the quantised confidences q_i over list t of the running best and total
+// their sum W over the pair (both below 2^32, exact in double); mass null: no winner yet.  For
+// a pair that is not weighted, mass = counts and total = n: the quotient above, the same bits.
+// For equal weights q, (q c) / (q n) and c / n are correctly rounded quotients of one rational:
+// the same bits again.
+inline uint32_t required_samples_mass(int s, int k_md, int k_pt, uint32_t total, const uint32_t *mass,
+                                      const StopOptions &o) {
+    const int ss[2][3] = {{k_md, k_md, 0}, {0, 0, k_pt}};
+    double p_all = 1.0;
+    for (int t = 0; t < 3; ++t) {
+        const double r = (total > 0 && mass) ? (double)mass[t] / (double)total : 0.0;
+        p_all *= std::pow(r, (double)ss[s][t]);
+    }
+    if (p_all <= 0.0) return o.max_num_iterations_per_solver;
+    if (p_all >= 1.0) return o.min_num_iterations;
+    const double p_bad = 1.0 - p_all;
+    if (p_bad >= 0.99999999999999) return o.max_num_iterations_per_solver;
+    const double it = std::ceil(std::log(1.0 - o.success_probability) / std::log(p_bad) + 0.5);
+    // (in double: `it` may be above 2^32, -inf, or NaN; !(it < max) takes the bound for all but -inf)
+    uint32_t r = o.max_num_iterations_per_solver;
+    if (it < (double)o.max_num_iterations_per_solver) r = it > 0.0 ? (uint32_t)it : 0u;
+    return std::max(o.min_num_iterations, r);
+}
+
+// the mass of three inlier lists (idx[offsets[t] .. offsets[t + 1]), indices in 0 .. n - 1) under
+// the table c[0 .. n]: the host form of kernels/inlier_mass.h's sums (uint32, wrapping only if
+// a list repeats rows)
+inline void inlier_mass_host(const uint32_t *cum, const int64_t offsets[4], const int32_t *idx, uint32_t mass[3]) {
+    for (int t = 0; t < 3; ++t) {
+        uint32_t m = 0u;
+        for (int64_t j = offsets[t]; j < offsets[t + 1]; ++j) m += cum[idx[j] + 1] - cum[idx[j]];
+        mass[t] = m;
+    }
+}
+
 // the stop test after a round: drawn[s] samples of type s so far
 inline bool stop_reached(const uint32_t req[2], const int64_t drawn[2]) {
     for (int s = 0; s < 2; ++s)

@@ -155,6 +155,17 @@ struct RelaxedSweepOut {
     double score;
     int count[3], relaxed[3];
 };
+// One item of inlier_mass_kernel (kernels/inlier_mass.h): the pair, and whether its rows weigh
+// their quantised confidences (the pair's table of mp_draw_weights_create) or 1 each.
+struct MassItem {
+    int pair, weighted;
+};
+// Its outcome: per term the weight mass and the length of the list err < thr, and the pair's
+// total (the table's last entry W, or n for an item that is not weighted).
+struct MassOut {
+    uint32_t mass[3], total;
+    int count[3], pad;
+};
 // One entry of mp_lsq_fit_set's launches (kernels/lsq_subset.h): a model of pair `pair` with
 // its own slice of the call's workspace, so a pair may occur in several entries of a launch.
 // The wide lists err < thr * factor go to ws + ws_off + t * stride (stride = the pair's n), the

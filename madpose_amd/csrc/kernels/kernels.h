@@ -163,6 +163,16 @@ hipError_t launch_refine_sweep_relaxed(hipStream_t s, int variant, const PairDat
 hipError_t launch_lm_pairs(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs, const LmJob *jobs,
                            const LmPairRef *refs, int njobs, const int *idx, Model *out, int *status);
 
+// The weight mass of a model's inlier lists (inlier_mass.h; mp_inlier_mass_set).  One workgroup
+// per item k = (pair, weighted) with model record recs[k]: out[k] = per term the sum of the
+// quantised weights q_i = c[i + 1] - c[i] and the number of the rows with err < thr (errors as
+// launch_refine_sweep's), c the pair's table at cum + tab_off[pair] (n + 1 entries), and total
+// = c[n]; an item that is not weighted takes q_i = 1 and total = n and reads no table (cum and
+// tab_off may be null when no item is weighted).  Nothing else is written.
+hipError_t launch_inlier_mass(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                              const MassItem *items, const ScoreRec *recs, int nitems, const uint32_t *cum,
+                              const int64_t *tab_off, MassOut *out);
+
 // Least-squares fits on random inlier subsets (lsq_subset.h; mp_lsq_fit_set).  One workgroup
 // per entry; entry k's model record is recs[k], its outcome out[k], its workspace slice ws +
 // entries[k].ws_off (6 * stride ints: the three wide lists, then the three subset lists, each
