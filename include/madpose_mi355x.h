@@ -899,6 +899,54 @@ int mp_debug_ransac_required_mass(int variant, uint32_t total, const uint32_t ma
 int mp_debug_inlier_mass_host(int64_t n, const uint32_t *cum /* n + 1 */, const int64_t offsets[4],
                               const int32_t *idx, uint32_t mass[3]);
 int mp_debug_inlier_mass_stats(int64_t *launches /* nullable */, double *ms /* nullable */, int32_t reset);
+/* Per-correspondence errors and inlier masks: what a model does to every correspondence of a
+ * resident pair.  The entry is additive; the entries above and their bytes are unchanged.
+ *
+ * mp_residuals_set: entry e = (pair pair_ids[e] (NULL: e), models[e] in user units, converted as
+ * every set stage converts them, factors[e] (NULL: 1.0)).  A pair may occur in any number of
+ * entries; at most 2^24 entries.  row_offsets[e] = the correspondences of the entries before e
+ * and R = row_offsets[num_entries]; entry e owns rows row_offsets[e] .. row_offsets[e + 1] - 1 of
+ * the outputs.  For row i of entry e, with err_t (t = 0: depth-aware reprojection 0 -> 1, 1: the
+ * same 1 -> 0, 2: Sampson) the squared errors every stage compares with the thresholds -- ungated:
+ * no score type replaces a term -- and thr_t the pair's thresholds:
+ *   mask[row_offsets[e] + i]: bit t set iff err_t < thr_t * factors[e], the product formed once in
+ *     double as mp_refine_relaxed_set and mp_lsq_fit_set form theirs (factor 1.0: thr_t itself);
+ *     bits 3 .. 7 zero; a NaN error is not an inlier, so a model with a NaN entry has mask 0;
+ *   errors[t * R + row_offsets[e] + i] = err_t (errors nullable; term-major (3, R) float64);
+ *   counts[3 e + t] = the rows of entry e with bit t set.
+ * With factor 1.0, bit t of row i is set iff i is in list t of mp_select_set for that single
+ * candidate, and counts are the list lengths.  The errors are in problem units: for the focal
+ * variants these are coordinates divided by the pair's normalization scale s
+ * (mp_pair_set_norm_scales), so s * s * err_t is in squared pixels; the library does not multiply.
+ * The MSAC score is not returned (mp_select_set returns it).  The call does not hypothesize, so
+ * every variant 0 .. 3 and every use_shift / MD solver setting is supported.
+ *
+ * Outputs: on_device 0 -- host arrays, filled through a device scratch in runs whose size does
+ * not grow with R.  on_device 1 -- memory of the set's device, checked before any launch as
+ * mp_pair_set_create_device checks its arrays (device memory of that device, errors aligned to 8
+ * bytes, the bytes inside the allocation's address range) and that the two ranges do not
+ * overlap; the kernel writes into it directly (no staging copy) and only into those R bytes and
+ * 3 R doubles.  The library's stream waits for an event recorded on producer_stream (a
+ * hipStream_t; NULL: the null stream) before its first write; the host does not wait for that
+ * stream.  The call returns after the library's own stream is synchronised.  It leaves nothing in
+ * the set that a later call can see.
+ * MP_EINVAL, before the device is touched: a NULL set, out, mask, row_offsets or counts; NULL
+ * models with num_entries > 0; num_entries negative or above 2^24; a pair outside the set;
+ * pair_ids NULL with num_entries != num_pairs; a factor that is not finite and > 0.
+ * mp_debug_residuals_stats: the stage's kernel launches since the last reset and, measured while
+ * profiling is enabled (mp_profile_enable), their summed device milliseconds. */
+typedef struct mp_residuals_out {
+    void *mask;            /* uint8, R bytes */
+    void *errors;          /* nullable; float64, 3 * R, term-major */
+    int32_t on_device;     /* 0: host arrays; 1: device memory of the set's device */
+    int32_t pad;
+    void *producer_stream; /* on_device only; NULL: the null stream */
+} mp_residuals_out;
+int mp_residuals_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_ids /* nullable: pair e */,
+                     const mp_model *models /* user units */, const double *factors /* nullable: 1.0 */,
+                     const mp_residuals_out *out, int64_t *row_offsets /* num_entries + 1 */,
+                     int32_t *counts /* 3 * num_entries */);
+int mp_debug_residuals_stats(int64_t *launches /* nullable */, double *ms /* nullable */, int32_t reset);
 /* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
  * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
  * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the

@@ -1619,6 +1619,153 @@ class PairSet:
         return [InlierMass(tuple(int(v) for v in q.mass), int(q.total), tuple(int(v) for v in q.count),
                            bool(q.weighted)) for q in res]
 
+    def residuals(self, models, pair_ids=None, factor=1.0, errors=False, out_mask=None, out_errors=None, stream=None):
+        """What models do to every correspondence (mp_residuals_set): a ResidualsResult with the
+        three-bit inlier mask and, with errors=True, the three squared errors of every row.
+
+        One entry per model; models is a sequence of pose objects or an (ne, 17) float64 array
+        in mp_model order (RansacResult.model_row, what select accepts); pair_ids (None: all
+        pairs in order) MAY repeat a pair; factor: the thresholds' factor, a scalar or one value
+        per entry.  Entry e owns rows res.rows(e) of the outputs.  mask[i]: bit t set iff
+        errors[t, i] < thr_t * factor (t = 0, 1: the depth-aware reprojection errors 0 -> 1 and
+        1 -> 0, t = 2: Sampson; ungated by the score type); with factor 1 bit t marks exactly
+        inlier_indices[t] of select([[m]], pair_ids=[p]), and counts are those lists' lengths.
+        A model with a NaN entry has an all-zero mask.  The errors are in problem units: for the
+        focal variants multiply by norm_scale[p] ** 2 for squared pixels.
+
+        Without out_mask / out_errors the results are host numpy arrays.  out_mask (uint8, shape
+        (R,)) and out_errors (float64, shape (3, R); implies errors=True), R the rows of the
+        call, are C-contiguous writable arrays of one kind: numpy arrays, or device arrays
+        (objects with __cuda_array_interface__, e.g. torch tensors on the set's device), which
+        the kernel writes directly; stream is then the stream they were last used on, as in
+        from_device.  ValueError, before any library call, for a wrong model count, shape or
+        dtype, a bad output shape, dtype, contiguity or read-only flag, a factor that is not
+        finite and positive, and outputs of different kinds."""
+        h = self._live()
+        P = len(self._sizes)
+        if isinstance(models, np.ndarray):
+            if models.dtype != np.float64 or models.ndim != 2 or models.shape[1] != 17:
+                raise ValueError(f"array models must be float64 of shape (ne, 17), got {models.dtype} {models.shape}")
+            ne = models.shape[0]
+        else:
+            try:
+                ne = len(models)
+            except TypeError:
+                raise ValueError("models must be a sequence of poses or an (ne, 17) float64 array") from None
+        if pair_ids is None:
+            if ne != P:
+                raise ValueError(f"one model per pair: {ne} for {P} pairs")
+            ids, ptr = None, None
+            sizes = list(self._sizes)
+        else:
+            ids = np.ascontiguousarray(np.asarray(pair_ids, dtype=np.int64).reshape(-1))
+            if len(ids) != ne:
+                raise ValueError(f"one model per entry: {ne} for {len(ids)} pair_ids")
+            for j, k in enumerate(ids.tolist()):
+                if not 0 <= k < P:
+                    raise ValueError(f"pair_ids[{j}] = {k} is outside the set of {P} pairs")
+            ids = ids.astype(np.int32)
+            ptr = ids.ctypes.data_as(L.c_int32_p)
+            sizes = [self._sizes[k] for k in ids.tolist()]
+        if ne > L.RESIDUALS_MAX_ENTRIES:
+            raise ValueError("at most 2^24 entries per call")
+        fa = np.asarray(factor)
+        if fa.dtype == np.bool_ or fa.dtype.kind not in "fiu":
+            raise ValueError("factor must be a number or one number per entry")
+        fa = np.ascontiguousarray(np.broadcast_to(fa, (ne,)) if fa.ndim == 0 else fa.reshape(-1), dtype=np.float64)
+        if len(fa) != ne:
+            raise ValueError(f"one factor value per entry: {len(fa)} for {ne}")
+        if not np.all(np.isfinite(fa) & (fa > 0)):
+            raise ValueError("factor must be finite and positive")
+        if not isinstance(errors, (bool, np.bool_)):
+            raise ValueError("errors must be True or False")
+        offs = np.zeros(ne + 1, dtype=np.int64)
+        np.cumsum(np.asarray(sizes, dtype=np.int64), out=offs[1:])
+        R = int(offs[-1])
+        want_err = bool(errors) or out_errors is not None
+
+        def output(a, name, typestrs, dtype, shape):
+            """(kind, address) of a caller's output array, checked"""
+            if isinstance(a, np.ndarray):
+                if a.dtype != dtype or a.shape != shape:
+                    raise ValueError(f"{name} must be {np.dtype(dtype).name} of shape {shape}, got {a.dtype} {a.shape}")
+                if not a.flags.c_contiguous:
+                    raise ValueError(f"{name} must be C-contiguous")
+                if not a.flags.writeable:
+                    raise ValueError(f"{name} is read-only")
+                return "host", a.ctypes.data
+            try:
+                cai = a.__cuda_array_interface__
+            except Exception as e:
+                raise ValueError(f"{name} must be a numpy array or a device array (an object with "
+                                 f"__cuda_array_interface__): {e}") from None
+            if cai.get("typestr") not in typestrs:
+                raise ValueError(f"{name} must be {np.dtype(dtype).name}, got typestr {cai.get('typestr')!r}")
+            shp = tuple(int(s) for s in cai.get("shape", ()))
+            if shp != shape:
+                raise ValueError(f"{name} must have shape {shape} (R = {R} rows), got {shp}")
+            strides = cai.get("strides")
+            if strides is not None:
+                item, want = np.dtype(dtype).itemsize, []
+                for s in reversed(shp):
+                    want.append(item)
+                    item *= s
+                if any(s > 1 and st != w for s, st, w in zip(shp, strides, reversed(want))):
+                    raise ValueError(f"{name} must be C-contiguous")
+            data = cai.get("data", (0, False))
+            if len(data) > 1 and data[1]:
+                raise ValueError(f"{name} is read-only")
+            if R > 0 and not data[0]:
+                raise ValueError(f"{name} has no device address")
+            return "device", int(data[0])
+
+        kinds = set()
+        mask_ptr = err_ptr = None
+        if out_mask is not None:
+            kind, mask_ptr = output(out_mask, "out_mask", ("|u1", "<u1", "=u1"), np.uint8, (R,))
+            kinds.add(kind)
+        if out_errors is not None:
+            kind, err_ptr = output(out_errors, "out_errors", ("<f8", "=f8"), np.float64, (3, R))
+            kinds.add(kind)
+        if len(kinds) > 1:
+            raise ValueError("out_mask and out_errors must be of one kind: both numpy arrays or both device arrays")
+        on_device = "device" in kinds
+        if on_device and (out_mask is None or (want_err and out_errors is None)):
+            raise ValueError("device outputs: out_mask is needed, and out_errors when errors are asked for")
+        producer = None
+        if stream is not None:
+            if not on_device:
+                raise ValueError("stream goes with device outputs")
+            handle = getattr(stream, "cuda_stream", stream)
+            if isinstance(handle, bool) or not isinstance(handle, int) or handle < 0:
+                raise ValueError("stream must be None, an integer stream handle or an object with .cuda_stream")
+            producer = handle or None
+        if isinstance(models, np.ndarray):
+            keep = np.ascontiguousarray(models)
+            arr = keep.ctypes.data_as(ctypes.POINTER(L.mp_model))
+        else:
+            keep = arr = (L.mp_model * max(ne, 1))(*[_model_to_c(m, self.variant) for m in models])
+
+        res = ResidualsResult()
+        res.mask = out_mask if out_mask is not None else np.zeros(R, dtype=np.uint8)
+        res.errors = out_errors if out_errors is not None else (np.zeros((3, R)) if want_err else None)
+        res.offsets = offs
+        res.counts = np.zeros((ne, 3), dtype=np.int32)
+        if R == 0:  # (no row: answered here, nothing to launch or write)
+            return res
+        out = L.mp_residuals_out()
+        out.mask = mask_ptr if out_mask is not None else res.mask.ctypes.data
+        out.errors = err_ptr if out_errors is not None else (res.errors.ctypes.data if want_err else None)
+        out.on_device = 1 if on_device else 0
+        out.producer_stream = producer
+        row_offsets = np.zeros(ne + 1, dtype=np.int64)
+        L.check(L.lib().mp_residuals_set(h, ne, ptr, arr, _dp(fa), ctypes.byref(out),
+                                         row_offsets.ctypes.data_as(L.c_int64_p),
+                                         res.counts.ctypes.data_as(L.c_int32_p)))
+        del keep
+        res.offsets = row_offsets
+        return res
+
     def _check_draw(self, budget, seed, point_share, ns):
         if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) or budget < 0:
             raise ValueError("budget must be a non-negative integer")
@@ -2043,6 +2190,27 @@ class InlierMass:
 
     def __repr__(self):
         return f"InlierMass(mass={self.mass} of {self.total}, count={self.count}, weighted={self.weighted})"
+
+
+class ResidualsResult:
+    """PairSet.residuals' outcome: offsets ((ne + 1,) int64: entry e owns rows offsets[e] ..
+    offsets[e + 1] - 1), counts ((ne, 3) int32: the entry's rows with bit t set), mask ((R,)
+    uint8, bits 0 .. 2: the row is an inlier of term t; a numpy array or the object passed as
+    out_mask) and errors ((3, R) float64 in problem units, the object passed as out_errors, or
+    None when not asked for)."""
+
+    def __init__(self):
+        self.offsets = None
+        self.counts = None
+        self.mask = None
+        self.errors = None
+
+    def rows(self, e):
+        """The rows of entry e, as a slice of mask and of errors' second axis."""
+        return slice(int(self.offsets[e]), int(self.offsets[e + 1]))
+
+    def __repr__(self):
+        return f"ResidualsResult(entries={len(self.counts)}, rows={int(self.offsets[-1])})"
 
 
 class LsqFitResult:

@@ -677,6 +677,29 @@ int mp_debug_inlier_mass_stats(int64_t *launches, double *ms, int32_t reset) {
     });
 }
 
+int mp_residuals_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_ids, const mp_model *models,
+                     const double *factors, const mp_residuals_out *out, int64_t *row_offsets, int32_t *counts) {
+    return guarded([&]() {
+        if (!set) throw std::invalid_argument("null pair set");
+        if (!out) throw std::invalid_argument("null out");
+        mp::ResidualsOut O;
+        O.mask = out->mask;
+        O.errors = out->errors;
+        O.on_device = out->on_device;
+        O.producer_stream = out->producer_stream;
+        mp::residuals_set(reinterpret_cast<mp::PairSet *>(set), num_entries, pair_ids,
+                          reinterpret_cast<const mp::Model *>(models), factors, O, row_offsets, counts);
+        return MP_OK;
+    });
+}
+
+int mp_debug_residuals_stats(int64_t *launches, double *ms, int32_t reset) {
+    return guarded([&]() {
+        mp::residuals_stats(launches, ms, reset != 0);
+        return MP_OK;
+    });
+}
+
 int mp_debug_draw_weights_host(int64_t n, const void *weights, int32_t dtype, uint32_t *cum, int32_t *positive) {
     return guarded([&]() {
         mp::draw_weights_host(n, weights, dtype, cum, positive);

@@ -4659,6 +4659,168 @@ void inlier_mass_host_hook(int64_t n, const uint32_t *cum, const int64_t *offset
     inlier_mass_host(cum, offsets, idx, mass);
 }
 
+// ---- the errors and inlier mask of every correspondence (mp_residuals_set) ----
+namespace {
+std::mutex g_resid_mu;
+int64_t g_resid_launches = 0;
+double g_resid_ms = 0.0;
+
+// residuals_set's checks, all before the device is touched
+void residuals_check(const PairSet *set, int32_t ne, const int32_t *pair_ids, const Model *models,
+                     const double *factors) {
+    if (!pair_ids && ne != set->num_pairs)
+        throw std::invalid_argument("num_entries must be the pair count without pair_ids");
+    for (int32_t e = 0; factors && e < ne; ++e)
+        if (!(std::isfinite(factors[e]) && factors[e] > 0.0))
+            throw std::invalid_argument("factors[" + std::to_string(e) + "] must be finite and > 0");
+    for (int32_t e = 0; pair_ids && e < ne; ++e)
+        if (pair_ids[e] < 0 || pair_ids[e] >= set->num_pairs)
+            throw std::invalid_argument("pair_ids[" + std::to_string(e) + "] is outside the set");
+    if (ne > 0 && !models) throw std::invalid_argument("null models");
+}
+} // namespace
+
+void residuals_stats(int64_t *launches, double *ms, bool reset) {
+    std::lock_guard<std::mutex> lk(g_resid_mu);
+    if (launches) *launches = g_resid_launches;
+    if (ms) *ms = g_resid_ms;
+    if (reset) g_resid_launches = 0, g_resid_ms = 0.0;
+}
+
+void residuals_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, const Model *models,
+                   const double *factors, const ResidualsOut &out, int64_t *row_offsets, int32_t *counts) {
+    if (!set) throw std::invalid_argument("null pair set");
+    if (!out.mask) throw std::invalid_argument("null mask");
+    if (!row_offsets || !counts) throw std::invalid_argument("null row_offsets or counts");
+    if (num_entries < 0 || num_entries > kResidEntriesMax)
+        throw std::invalid_argument("num_entries must be in 0..2^24");
+    std::lock_guard<std::mutex> lk(set->mu);
+    residuals_check(set, num_entries, pair_ids, models, factors);
+    row_offsets[0] = 0;
+    if (num_entries == 0) return;
+    const int32_t ne = num_entries;
+    ResidentPairs &R = *set->R;
+    const int variant = R.variant;
+    std::vector<int32_t> pairs((size_t)ne);
+    std::vector<int64_t> sizes((size_t)ne);
+    for (int32_t e = 0; e < ne; ++e) {
+        pairs[(size_t)e] = pair_ids ? pair_ids[e] : e;
+        sizes[(size_t)e] = R.n[(size_t)pairs[(size_t)e]];
+    }
+    resid_offsets(ne, sizes.data(), row_offsets);
+    std::fill(counts, counts + 3 * (size_t)ne, 0);
+    const int64_t rows = row_offsets[ne];
+    if (rows == 0) return; // (no row: nothing is launched or written)
+    const bool dev = out.on_device != 0, want_err = out.errors != nullptr;
+
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+    struct Event { // (destroyed after the last synchronise, or on the way out)
+        hipEvent_t ev = nullptr;
+        ~Event() {
+            if (ev) (void)hipEventDestroy(ev);
+        }
+    } produced, t0, t1;
+    if (dev) {
+        // ---- both device pointers, before any launch or copy ----
+        const int64_t mb = resid_mask_bytes(rows), eb = resid_error_bytes(rows);
+        check_device_array("mask", out.mask, mb, 1, set->device);
+        if (want_err) {
+            check_device_array("errors", out.errors, eb, 8, set->device);
+            if (resid_overlap((uint64_t)(uintptr_t)out.mask, mb, (uint64_t)(uintptr_t)out.errors, eb))
+                throw std::invalid_argument("device arrays mask and errors overlap");
+        }
+        // ---- the producer's work first: an event on its stream, no host wait ----
+        MP_HIP(hipEventCreateWithFlags(&produced.ev, hipEventDisableTiming));
+        MP_HIP(hipEventRecord(produced.ev, static_cast<hipStream_t>(out.producer_stream)));
+        MP_HIP(hipStreamWaitEvent(stream, produced.ev, 0));
+    }
+    const bool timed = g_prof_on.load();
+    if (timed) {
+        MP_HIP(hipEventCreate(&t0.ev));
+        MP_HIP(hipEventCreate(&t1.ev));
+    }
+
+    // (MADPOSE_RESIDUALS_RUN_ROWS / _RUN_ENTRIES: smaller runs, for the tests of the cut)
+    const int64_t row_bound = dev ? kResidRunRowsDevice : kResidRunRows;
+    const int64_t run_rows = env_int("MADPOSE_RESIDUALS_RUN_ROWS", row_bound, 1, row_bound);
+    const int32_t run_entries = (int32_t)env_int("MADPOSE_RESIDUALS_RUN_ENTRIES", kResidRunEntries, 1, kResidRunEntries);
+    std::vector<ResidRun> runs;
+    resid_runs(ne, row_offsets, run_rows, run_entries, runs);
+    size_t max_e = 0, max_items = 0;
+    int64_t max_rows = 0;
+    for (const ResidRun &r : runs) {
+        max_e = std::max(max_e, (size_t)(r.e1 - r.e0));
+        // (an entry of n rows has ceil(n / kResidItemRows) <= n / kResidItemRows + 1 items)
+        max_items = std::max(max_items, (size_t)(r.e1 - r.e0) + (size_t)(r.rows / kResidItemRows));
+        max_rows = std::max(max_rows, r.rows);
+    }
+    DevArray<ScoreRec> d_recs(max_e);
+    DevArray<ResidItem> d_items(max_items);
+    DevArray<ResidCount> d_cnt(max_items);
+    // host outputs: the scratch of one run (device outputs are written in place)
+    std::unique_ptr<DevArray<unsigned char>> d_mask;
+    std::unique_ptr<DevArray<double>> d_err;
+    if (!dev) {
+        d_mask.reset(new DevArray<unsigned char>((size_t)max_rows));
+        if (want_err) d_err.reset(new DevArray<double>(3 * (size_t)max_rows));
+    }
+    std::vector<ScoreRec> recs;
+    std::vector<ResidItem> items;
+    std::vector<int64_t> first_item;
+    std::vector<ResidCount> cnt;
+    int64_t launches = 0;
+    double ms = 0.0;
+    for (const ResidRun &r : runs) {
+        if (r.rows == 0) continue; // (entries without correspondences: their counts are 0)
+        recs.resize((size_t)(r.e1 - r.e0));
+        for (int32_t e = r.e0; e < r.e1; ++e) {
+            const int k = pairs[(size_t)e];
+            Model c = models[e];
+            if (variant == kSF || variant == kTF) {
+                c.focal0 /= R.norm_scale[(size_t)k];
+                c.focal1 /= R.norm_scale[(size_t)k];
+            }
+            prepare_score_rec(R.Ch[(size_t)k], c, recs[(size_t)(e - r.e0)]);
+        }
+        resid_items(r, pairs.data(), factors, row_offsets, dev ? 0 : r.row0, items, first_item);
+        if (items.size() > max_items) throw std::logic_error("residuals: more items than planned");
+        cnt.resize(items.size());
+        unsigned char *mask = dev ? static_cast<unsigned char *>(out.mask) : d_mask->p;
+        double *err = !want_err ? nullptr : dev ? static_cast<double *>(out.errors) : d_err->p;
+        const int64_t stride = dev ? rows : r.rows;
+        MP_HIP(hipMemcpyAsync(d_recs.p, recs.data(), sizeof(ScoreRec) * recs.size(), hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(ResidItem) * items.size(), hipMemcpyHostToDevice,
+                              stream));
+        if (timed) MP_HIP(hipEventRecord(t0.ev, stream));
+        MP_HIP(launch_residuals(stream, R.v, R.d_D.p, R.d_C.p, d_items.p, (int)items.size(), d_recs.p, mask, err,
+                                stride, d_cnt.p));
+        if (timed) MP_HIP(hipEventRecord(t1.ev, stream));
+        MP_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(ResidCount) * items.size(), hipMemcpyDeviceToHost, stream));
+        if (!dev) {
+            MP_HIP(hipMemcpyAsync(static_cast<unsigned char *>(out.mask) + r.row0, d_mask->p, (size_t)r.rows,
+                                  hipMemcpyDeviceToHost, stream));
+            for (int t = 0; want_err && t < 3; ++t)
+                MP_HIP(hipMemcpyAsync(static_cast<double *>(out.errors) + (int64_t)t * rows + r.row0,
+                                      d_err->p + (int64_t)t * r.rows, sizeof(double) * (size_t)r.rows,
+                                      hipMemcpyDeviceToHost, stream));
+        }
+        MP_HIP(hipStreamSynchronize(stream)); // (recs, items and the scratch are reused by the next run)
+        if (timed) {
+            float f = 0.f;
+            MP_HIP(hipEventElapsedTime(&f, t0.ev, t1.ev));
+            ms += f;
+        }
+        ++launches;
+        for (int32_t e = r.e0; e < r.e1; ++e)
+            for (int64_t j = first_item[(size_t)(e - r.e0)]; j < first_item[(size_t)(e - r.e0) + 1]; ++j)
+                for (int t = 0; t < 3; ++t) counts[3 * (size_t)e + t] += cnt[(size_t)j].count[t];
+    }
+    std::lock_guard<std::mutex> sl(g_resid_mu);
+    g_resid_launches += launches;
+    g_resid_ms += ms;
+}
+
 RansacTiming ransac_timing_last() {
     std::lock_guard<std::mutex> lk(g_ransac_mu);
     return g_ransac_timing;

@@ -389,6 +389,32 @@ void inlier_mass_set(PairSet *set, const DrawWeights *weights, int32_t num_entri
 void ransac_required_mass(int variant, uint32_t total, const uint32_t *mass, const RansacOptions &opts, uint32_t *req);
 void inlier_mass_host_hook(int64_t n, const uint32_t *cum, const int64_t *offsets, const int32_t *idx, uint32_t *mass);
 void inlier_mass_stats(int64_t *launches, double *ms, bool reset);
+// The errors and inlier mask of every correspondence under given models (mp_residuals_set;
+// kernels/residuals.h, host/residuals_plan.h).  Entry e is the model models[e] (user units) of
+// pair pair_ids[e] (null: e; a pair MAY repeat) under the thresholds times factors[e] (null:
+// 1.0).  row_offsets (num_entries + 1): entry e's rows; counts (3 per entry): its rows with
+// err_t < thr_t * factor.  out.mask (R bytes, R = row_offsets[num_entries]): bit t of row i;
+// out.errors (nullable; 3 R doubles, term-major): the ungated errors in problem units, the
+// numbers compared.  on_device 0: host arrays, filled through a device scratch in runs whose
+// size does not grow with R.  on_device 1: memory of the set's device, checked as
+// pair_set_create_device checks its arrays (and that the two do not overlap) before any
+// launch; the kernel writes into it directly, ordered after producer_stream (null: the null
+// stream) by an event.  Returns after the library's stream is synchronised.  Nothing of the
+// set is written.  std::invalid_argument before the device is touched: a null set, mask,
+// row_offsets, counts or models; num_entries outside 0 .. 2^24; a pair outside the set; null
+// pair_ids with num_entries != the pair count; a factor that is not finite and > 0.
+struct ResidualsOut {
+    void *mask = nullptr;
+    void *errors = nullptr;
+    int32_t on_device = 0, pad = 0;
+    void *producer_stream = nullptr;
+};
+void residuals_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, const Model *models,
+                   const double *factors, const ResidualsOut &out, int64_t *row_offsets, int32_t *counts);
+// residuals_stats (mp_debug_residuals_stats): the kernel launches since the last reset and
+// their summed device milliseconds (events around each launch; measured only while profiling
+// is enabled).
+void residuals_stats(int64_t *launches, double *ms, bool reset);
 // ransac_adaptive_set (mp_ransac_adaptive_set): ransac_set's drawn mode with a per-pair
 // number of samples.  Samples go through draw -> hypothesize_run -> select_run in rounds of
 // `step` per still-active pair (checkpoints m_k = min(k step, budget)); select_run continues

@@ -4,6 +4,7 @@
 
 #include "../host/ingest_plan.h"
 #include "../host/pair_set_plan.h"
+#include "../host/residuals_plan.h"
 #include "../include/mp_draw.h"
 #include "../include/mp_types.h"
 
@@ -172,6 +173,16 @@ hipError_t launch_lm_pairs(hipStream_t s, int variant, const PairData *Ds, const
 hipError_t launch_inlier_mass(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
                               const MassItem *items, const ScoreRec *recs, int nitems, const uint32_t *cum,
                               const int64_t *tab_off, MassOut *out);
+
+// The errors and the inlier mask of every correspondence (residuals.h; mp_residuals_set).  One
+// workgroup per item k (host/residuals_plan.h): rows first .. first + count - 1 of pair
+// items[k].pair under the record recs[items[k].rec].  Row first + j of it: mask[row + j] = bit t
+// set iff err_t < thr_t * factor (errors as launch_refine_sweep's), and, errors not null,
+// errors[t * stride + row + j] = err_t; out[k] = the item's three inlier counts.  Nothing else
+// is written.  mask / errors may be memory of the caller.
+hipError_t launch_residuals(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                            const ResidItem *items, int nitems, const ScoreRec *recs, unsigned char *mask,
+                            double *errors, int64_t stride, ResidCount *out);
 
 // Least-squares fits on random inlier subsets (lsq_subset.h; mp_lsq_fit_set).  One workgroup
 // per entry; entry k's model record is recs[k], its outcome out[k], its workspace slice ws +

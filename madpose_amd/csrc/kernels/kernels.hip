@@ -1826,6 +1826,8 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 #include "refine_batch.h"
 // the weight mass of a model's inlier lists (mp_inlier_mass_set, the weighted stopping rule)
 #include "inlier_mass.h"
+// the errors and inlier mask of every correspondence under given models (mp_residuals_set)
+#include "residuals.h"
 // least-squares fits on random inlier subsets, many entries per launch (mp_lsq_fit_set)
 #include "lsq_subset.h"
 // ranking of candidate models over many resident pairs (mp_select_batch)
