@@ -947,6 +947,69 @@ int mp_residuals_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_
                      const mp_residuals_out *out, int64_t *row_offsets /* num_entries + 1 */,
                      int32_t *counts /* 3 * num_entries */);
 int mp_debug_residuals_stats(int64_t *launches /* nullable */, double *ms /* nullable */, int32_t reset);
+/* RANSAC results into the caller's device arrays.  The entry is additive; the six ransac entries
+ * above and their bytes are unchanged.
+ *
+ * mp_ransac_out_set takes the union of their arguments and runs the body they choose: handle
+ * (nullable: the uniform draw); step 0: mp_ransac_set's fixed budget, its samples drawn (budget >=
+ * 0, sample_* NULL) or given (budget -1); step >= 1: the adaptive rounds, with lo_rounds (0: none)
+ * and lo_steps (0: none; needs lo_rounds) as mp_ransac_lo_set / mp_ransac_lo_steps_set take them;
+ * weighted_stop != 0: mp_ransac_weighted_stop_set's rule (needs handle and step >= 1).  stopped,
+ * lo_info, steps_info and rule_mass are the chosen body's (lo_info is needed with lo_rounds,
+ * steps_info with lo_steps; the others are nullable).  models and results are what that body
+ * returns, byte for byte.  inlier_idx is nullable: NULL copies no index list back from the device.
+ * Where a refinement follows (rounds >= 1) the selection's lists are not copied back at all, as
+ * every winner's lists are written again by the refinement.
+ *
+ * out (nullable; each of its five arrays nullable): memory of the set's device.  With ns = num_sel
+ * and offs[j] the correspondences of the selected pairs before entry j, R = offs[ns]:
+ *   models[17 j ..]: the bytes of models[j];  index[j] = results[j].best_candidate;
+ *   counts[3 j + t] = results[j].num_inliers[t];
+ *   mask[offs[j] + i]: bit t set iff i is in the returned list t of entry j; bits 3 .. 7 zero;
+ *   errors[t R + offs[j] + i]: the squared error err_t of row i, in problem units (see
+ *     mp_residuals_set), under the model the returned lists were formed from, kept in problem
+ *     units by the library -- so (errors[t R + row] < thr_t) == bit t of mask[row] on every row, in
+ *     every variant and after any number of rounds, which mp_residuals_set on the returned model
+ *     cannot promise for a refined focal model (it divides the returned focal by the
+ *     normalization scale again).  errors needs mask.
+ * For an entry without a winner (best_candidate -1), or without a correspondence: mask rows 0,
+ * error rows NaN, models row zeros, index -1, counts 0.  Every element of every given array that
+ * belongs to the selection is written exactly once per call, by a kernel (no copy into and no
+ * memset on the caller's memory), and nothing outside it.  Before any launch each array is checked
+ * as mp_residuals_set checks its device outputs (device memory of the set's device; errors and
+ * models aligned to 8 bytes, index and counts to 4; the bytes inside the allocation's address
+ * range, the byte counts overflow-checked) and the five ranges must be pairwise disjoint.  The
+ * library's stream waits for an event recorded on producer_stream (NULL: the null stream) before
+ * its first write; the host does not wait for that stream.  The call returns after the library's
+ * own stream is synchronised.  The output stage sums its per-item counts per pair and compares
+ * them with num_inliers: a difference is an internal error (MP_EDEVICE).
+ * MP_EINVAL, before the device is touched: a NULL set; errors without mask; any output array
+ * together with lo_rounds >= 1 and rounds = 0 -- without final rounds the overall best's lists may
+ * be those a local optimisation returned, and its model in problem units is not kept --; negative
+ * step, lo_rounds or lo_steps; lo_rounds or lo_steps with step 0; lo_steps without lo_rounds;
+ * weighted_stop without handle or step; given samples with step >= 1 or with handle; and the
+ * chosen body's own refusals.
+ * mp_debug_ransac_out_stats: the output stage's row launches since the last reset and, measured
+ * while profiling is enabled (mp_profile_enable), their summed device milliseconds. */
+typedef struct mp_ransac_out {
+    void *mask;            /* nullable; uint8, R bytes */
+    void *errors;          /* nullable; float64, 3 * R, term-major; needs mask */
+    void *models;          /* nullable; float64, 17 * num_sel */
+    void *index;           /* nullable; int32, num_sel */
+    void *counts;          /* nullable; int32, 3 * num_sel */
+    void *producer_stream; /* NULL: the null stream */
+} mp_ransac_out; /* 48 bytes */
+int mp_ransac_out_set(mp_pair_set *set, const mp_draw_weights *handle /* nullable */, int32_t num_sel,
+                      const int32_t *pair_ids, int32_t budget, int32_t step /* 0: a fixed budget */, uint64_t seed,
+                      int32_t point_share, const int64_t *sample_offsets /* nullable */,
+                      const int32_t *sample_types /* nullable */, const int32_t *sample_idx /* nullable */,
+                      int32_t rounds, int32_t lo_rounds /* 0: none */, int32_t lo_steps /* 0: none */,
+                      int32_t weighted_stop, mp_model *models /* num_sel */, mp_ransac_result *results /* num_sel */,
+                      int32_t *inlier_idx /* nullable: no lists */, int32_t *stopped /* num_sel, nullable */,
+                      mp_ransac_lo_info *lo_info, mp_ransac_lo_steps_info *steps_info, int64_t sample_chunk,
+                      int64_t model_chunk, mp_inlier_mass *rule_mass /* num_sel, nullable */,
+                      const mp_ransac_out *out /* nullable */);
+int mp_debug_ransac_out_stats(int64_t *launches /* nullable */, double *ms /* nullable */, int32_t reset);
 /* Measurement hook (tools/ransac_set_bench.py): the last mp_ransac_set made while profiling
  * was enabled (mp_profile_enable), every stage waited for -- ms: the call, its hypothesis /
  * select / refine stages; of the hypothesis stage: host planning, the sampler, uploads, the

@@ -239,6 +239,18 @@ class mp_residuals_out(ctypes.Structure):
 
 RESIDUALS_MAX_ENTRIES = 1 << 24  # mp_residuals_set's entries per call
 
+
+class mp_ransac_out(ctypes.Structure):
+    _fields_ = [
+        ("mask", ctypes.c_void_p),
+        ("errors", ctypes.c_void_p),
+        ("models", ctypes.c_void_p),
+        ("index", ctypes.c_void_p),
+        ("counts", ctypes.c_void_p),
+        ("producer_stream", ctypes.c_void_p),
+    ]
+
+
 # the weighted draw: the largest pair that may be given weights, the table entries (n + 1) the
 # device sampler reads through LDS (MP_DRAW_WEIGHT_MAX_N, MP_DRAW_STAGE_ENTRIES)
 DRAW_WEIGHT_MAX_N, DRAW_STAGE_ENTRIES = 65535, 4096
@@ -353,6 +365,14 @@ EXPORTS = {
     "mp_residuals_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.POINTER(mp_model),
                                         c_double_p, ctypes.POINTER(mp_residuals_out), c_int64_p, c_int32_p]),
     "mp_debug_residuals_stats": (ctypes.c_int, [c_int64_p, c_double_p, ctypes.c_int32]),
+    "mp_ransac_out_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int32,
+                                         ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, c_int64_p, c_int32_p,
+                                         c_int32_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                         ctypes.POINTER(mp_model), ctypes.POINTER(mp_ransac_result), c_int32_p,
+                                         c_int32_p, ctypes.POINTER(mp_ransac_lo_info),
+                                         ctypes.POINTER(mp_ransac_lo_steps_info), ctypes.c_int64, ctypes.c_int64,
+                                         ctypes.POINTER(mp_inlier_mass), ctypes.POINTER(mp_ransac_out)]),
+    "mp_debug_ransac_out_stats": (ctypes.c_int, [c_int64_p, c_double_p, ctypes.c_int32]),
     "mp_debug_draw_weights_host": (ctypes.c_int, [ctypes.c_int64, ctypes.c_void_p, ctypes.c_int32,
                                                   ctypes.POINTER(ctypes.c_uint32), c_int32_p]),
     "mp_debug_draw_weighted_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int64, ctypes.POINTER(ctypes.c_uint32),

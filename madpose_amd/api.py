@@ -1184,6 +1184,48 @@ def _device_array(a, name, shape):
     return (int(ptr) or None), code, shp
 
 
+def _output_array(a, name, typestrs, dtype, shape, note):
+    """(kind, address) of a caller's output array, checked: a numpy array ("host") or an object
+    with __cuda_array_interface__ ("device") of the given dtype and shape, C-contiguous and
+    writable.  note: what the shape stands for, for the message.  ValueError otherwise; the
+    object is only inspected."""
+    if isinstance(a, np.ndarray):
+        if a.dtype != dtype or a.shape != shape:
+            raise ValueError(f"{name} must be {np.dtype(dtype).name} of shape {shape}, got {a.dtype} {a.shape}")
+        if not a.flags.c_contiguous:
+            raise ValueError(f"{name} must be C-contiguous")
+        if not a.flags.writeable:
+            raise ValueError(f"{name} is read-only")
+        return "host", a.ctypes.data
+    try:
+        cai = a.__cuda_array_interface__
+    except Exception as e:
+        raise ValueError(f"{name} must be a numpy array or a device array (an object with "
+                         f"__cuda_array_interface__): {e}") from None
+    if cai.get("typestr") not in typestrs:
+        raise ValueError(f"{name} must be {np.dtype(dtype).name}, got typestr {cai.get('typestr')!r}")
+    shp = tuple(int(s) for s in cai.get("shape", ()))
+    if shp != shape:
+        raise ValueError(f"{name} must have shape {shape} ({note}), got {shp}")
+    strides = cai.get("strides")
+    if strides is not None:
+        item, want = np.dtype(dtype).itemsize, []
+        for s in reversed(shp):
+            want.append(item)
+            item *= s
+        if any(s > 1 and st != w for s, st, w in zip(shp, strides, reversed(want))):
+            raise ValueError(f"{name} must be C-contiguous")
+    data = cai.get("data", (0, False))
+    if len(data) > 1 and data[1]:
+        raise ValueError(f"{name} is read-only")
+    size = 1
+    for s in shp:
+        size *= s
+    if size > 0 and not data[0]:
+        raise ValueError(f"{name} has no device address")
+    return "device", int(data[0])
+
+
 class PairSet:
     """Pairs set up once and resident on the device (mp_pair_set_*): hypothesize, select
     and refine as methods on them.
@@ -1684,48 +1726,14 @@ class PairSet:
         R = int(offs[-1])
         want_err = bool(errors) or out_errors is not None
 
-        def output(a, name, typestrs, dtype, shape):
-            """(kind, address) of a caller's output array, checked"""
-            if isinstance(a, np.ndarray):
-                if a.dtype != dtype or a.shape != shape:
-                    raise ValueError(f"{name} must be {np.dtype(dtype).name} of shape {shape}, got {a.dtype} {a.shape}")
-                if not a.flags.c_contiguous:
-                    raise ValueError(f"{name} must be C-contiguous")
-                if not a.flags.writeable:
-                    raise ValueError(f"{name} is read-only")
-                return "host", a.ctypes.data
-            try:
-                cai = a.__cuda_array_interface__
-            except Exception as e:
-                raise ValueError(f"{name} must be a numpy array or a device array (an object with "
-                                 f"__cuda_array_interface__): {e}") from None
-            if cai.get("typestr") not in typestrs:
-                raise ValueError(f"{name} must be {np.dtype(dtype).name}, got typestr {cai.get('typestr')!r}")
-            shp = tuple(int(s) for s in cai.get("shape", ()))
-            if shp != shape:
-                raise ValueError(f"{name} must have shape {shape} (R = {R} rows), got {shp}")
-            strides = cai.get("strides")
-            if strides is not None:
-                item, want = np.dtype(dtype).itemsize, []
-                for s in reversed(shp):
-                    want.append(item)
-                    item *= s
-                if any(s > 1 and st != w for s, st, w in zip(shp, strides, reversed(want))):
-                    raise ValueError(f"{name} must be C-contiguous")
-            data = cai.get("data", (0, False))
-            if len(data) > 1 and data[1]:
-                raise ValueError(f"{name} is read-only")
-            if R > 0 and not data[0]:
-                raise ValueError(f"{name} has no device address")
-            return "device", int(data[0])
-
         kinds = set()
         mask_ptr = err_ptr = None
         if out_mask is not None:
-            kind, mask_ptr = output(out_mask, "out_mask", ("|u1", "<u1", "=u1"), np.uint8, (R,))
+            kind, mask_ptr = _output_array(out_mask, "out_mask", ("|u1", "<u1", "=u1"), np.uint8, (R,), f"R = {R} rows")
             kinds.add(kind)
         if out_errors is not None:
-            kind, err_ptr = output(out_errors, "out_errors", ("<f8", "=f8"), np.float64, (3, R))
+            kind, err_ptr = _output_array(out_errors, "out_errors", ("<f8", "=f8"), np.float64, (3, R),
+                                          f"R = {R} rows")
             kinds.add(kind)
         if len(kinds) > 1:
             raise ValueError("out_mask and out_errors must be of one kind: both numpy arrays or both device arrays")
@@ -1932,7 +1940,8 @@ class PairSet:
                  slot[moffs[j]:moffs[j + 1]].copy()) for j in range(ns)]
 
     def ransac(self, budget=None, seed=0, point_share=None, samples=None, rounds=3, pair_ids=None, sample_chunk=0,
-               model_chunk=0, step=None, lo=None, lo_steps=None, weights=None, weighted_stop=False):
+               model_chunk=0, step=None, lo=None, lo_steps=None, weights=None, weighted_stop=False, out_mask=None,
+               out_errors=None, out_models=None, out_index=None, out_counts=None, stream=None, lists=True):
         """Fixed-budget RANSAC on the selected pairs in one call (mp_ransac_set): draw ->
         hypothesize -> select -> refine on the device-resident pairs.  Exactly one of budget
         (samples drawn on the device as draw(budget, seed, point_share) draws them) and samples
@@ -1995,7 +2004,54 @@ class PairSet:
         carry the confidence, stop much earlier.  Each mode's identity above still holds at
         r.num_samples.  r.rule_mass (a tuple of 3) and r.rule_total: what the rule last read
         for the pair (zeros and the pair's total when it never had a winner); None and 0 with
-        weighted_stop off."""
+        weighted_stop off.
+
+        out_mask, out_errors, out_models, out_index, out_counts (any subset; every mode above):
+        the results written into the caller's device arrays by the call itself
+        (mp_ransac_out_set).  With ns selected pairs in selection order and R the sum of their
+        sizes, pair j owns rows r.rows of out_mask (uint8, (R,)) and of the second axis of
+        out_errors (float64, (3, R); needs out_mask), and row j of out_models (float64, (ns, 17)),
+        out_index (int32, (ns,)) and out_counts (int32, (ns, 3)).  All are device arrays (objects
+        with __cuda_array_interface__, e.g. torch tensors) on the set's device, C-contiguous,
+        writable and disjoint; stream is the stream they were last used on, as in residuals.  For a
+        pair with a winner out_models[j] holds r.model_row's bytes, out_index[j] = r.index,
+        out_counts[j] the three list lengths, bit t of out_mask[row] is set iff the row is in
+        r.inlier_indices[t] (bits 3 .. 7 zero), and out_errors[t, row] is the squared error in
+        problem units under the model the lists were formed from -- so (out_errors[t] < thr_t)
+        equals bit t on every row, in every variant and after any number of rounds, where
+        residuals(r.model_row) can differ on a refined focal model.  For a pair without a winner,
+        or of size 0: mask rows 0, error rows NaN, model row zeros, index -1, counts 0.  Every
+        element belonging to the selection is written once; nothing else is touched.  Device
+        outputs together with lo and rounds=0 are refused: the overall best's lists may then be a
+        local optimisation's, whose model in problem units is not kept.
+
+        lists (a bool): False copies no index list back from the device -- r.inlier_indices is
+        None, r.num_inliers still holds the three lengths -- with or without device outputs.
+        r.rows: the pair's slice of out_mask and of out_errors' second axis (None when neither
+        was given).  Every other field, and the list itself, is what the call returns without
+        these arguments."""
+        if not isinstance(lists, (bool, np.bool_)):
+            raise ValueError("lists must be a bool")
+        outs = (("out_mask", out_mask), ("out_errors", out_errors), ("out_models", out_models),
+                ("out_index", out_index), ("out_counts", out_counts))
+        on_device = any(a is not None for _, a in outs)
+        for name, a in outs:
+            if isinstance(a, np.ndarray):
+                raise ValueError(f"{name} must be a device array (an object with __cuda_array_interface__): on the "
+                                 "host, r.inlier_indices holds the lists and PairSet.residuals fills numpy arrays")
+        if out_errors is not None and out_mask is None:
+            raise ValueError("out_errors needs out_mask")
+        if on_device and lo is not None and not isinstance(rounds, bool) and rounds == 0:
+            raise ValueError("device outputs with lo need rounds >= 1: without final rounds the overall best's lists "
+                             "may be a local optimisation's, whose model in problem units is not kept")
+        producer = None
+        if stream is not None:
+            if not on_device:
+                raise ValueError("stream goes with device outputs")
+            handle = getattr(stream, "cuda_stream", stream)
+            if isinstance(handle, bool) or not isinstance(handle, int) or handle < 0:
+                raise ValueError("stream must be None, an integer stream handle or an object with .cuda_stream")
+            producer = handle or None
         if not isinstance(weighted_stop, (bool, np.bool_)):
             raise ValueError("weighted_stop must be a bool")
         if weighted_stop and weights is None:
@@ -2045,6 +2101,27 @@ class PairSet:
                 raise ValueError(f"at most 2^22 samples per round, got {ns} pairs x {min(budget, int(step))}")
         elif samples is None:
             budget, seed, share = self._check_draw(budget, seed, point_share, ns)
+        R = offs[-1]
+        ptrs = {}
+        if on_device:
+            spans = []
+            for name, a, typestrs, dtype, shape, note in (
+                    ("out_mask", out_mask, ("|u1", "<u1", "=u1"), np.uint8, (R,), f"R = {R} rows"),
+                    ("out_errors", out_errors, ("<f8", "=f8"), np.float64, (3, R), f"R = {R} rows"),
+                    ("out_models", out_models, ("<f8", "=f8"), np.float64, (ns, 17), f"{ns} selected pairs"),
+                    ("out_index", out_index, ("<i4", "=i4"), np.int32, (ns,), f"{ns} selected pairs"),
+                    ("out_counts", out_counts, ("<i4", "=i4"), np.int32, (ns, 3), f"{ns} selected pairs")):
+                if a is None:
+                    continue
+                _, ptr_a = _output_array(a, name, typestrs, dtype, shape, note)
+                nbytes = int(np.prod(shape, dtype=np.int64)) * np.dtype(dtype).itemsize
+                if nbytes > 0:
+                    ptrs[name] = ptr_a
+                    spans.append((ptr_a, nbytes, name))
+            spans.sort()
+            for (a0, n0, name0), (a1, _, name1) in zip(spans, spans[1:]):
+                if a1 - a0 < n0:
+                    raise ValueError(f"{name0} and {name1} overlap")
         if ns == 0:
             return []
         if samples is None:
@@ -2060,7 +2137,24 @@ class PairSet:
         idx = np.zeros(3 * max(offs[-1], 1), dtype=np.int32)
         stopped = np.zeros(ns, dtype=np.int32)
         info = sinfo = rmass = None
-        if wh is not None and weighted_stop:
+        if on_device or not lists:
+            if lo is not None:
+                info = (L.mp_ransac_lo_info * ns)()
+            if lo_steps is not None:
+                sinfo = (L.mp_ransac_lo_steps_info * ns)()
+            if weighted_stop:
+                rmass = (L.mp_inlier_mass * ns)()
+            dev = L.mp_ransac_out()
+            dev.mask, dev.errors = ptrs.get("out_mask"), ptrs.get("out_errors")
+            dev.models, dev.index, dev.counts = ptrs.get("out_models"), ptrs.get("out_index"), ptrs.get("out_counts")
+            dev.producer_stream = producer
+            L.check(L.lib().mp_ransac_out_set(h, wh, ns, ptr, budget, 0 if step is None else int(step), seed, share, so,
+                                              ty, ix, int(rounds), 0 if lo is None else int(lo),
+                                              0 if lo_steps is None else int(lo_steps), 1 if weighted_stop else 0,
+                                              arr, res, idx.ctypes.data_as(L.c_int32_p) if lists else None,
+                                              stopped.ctypes.data_as(L.c_int32_p), info, sinfo, int(sample_chunk),
+                                              int(model_chunk), rmass, ctypes.byref(dev) if on_device else None))
+        elif wh is not None and weighted_stop:
             if lo is not None:
                 info = (L.mp_ransac_lo_info * ns)()
             if lo_steps is not None:
@@ -2128,7 +2222,10 @@ class PairSet:
             r.model_row = np.frombuffer(bytes(arr[j]), dtype=np.float64).copy()
             r.model = _model_from_c(arr[j], self.variant) if r.index >= 0 else None
             base = 3 * offs[j]
-            r.inlier_indices = [idx[base + t * n: base + t * n + q.num_inliers[t]].copy() for t in range(3)]
+            r.num_inliers = tuple(int(q.num_inliers[t]) for t in range(3))
+            r.inlier_indices = ([idx[base + t * n: base + t * n + q.num_inliers[t]].copy() for t in range(3)]
+                                if lists else None)
+            r.rows = slice(offs[j], offs[j + 1]) if out_mask is not None else None
             out.append(r)
         return out
 
@@ -2250,7 +2347,10 @@ class RansacResult:
     that produced the returned start model, -1 when no step did, and the steps' offers to the
     overall best and those accepted; -1, -1, 0 and 0 otherwise); rule_mass, rule_total
     (ransac(weighted_stop=True) only: the three weight masses and the total the termination rule
-    last read for the pair; None and 0 otherwise)."""
+    last read for the pair; None and 0 otherwise); num_inliers (a tuple of 3: the lengths of the
+    returned model's three lists, also with ransac(lists=False), where inlier_indices is None);
+    rows (ransac(out_mask=...) only: the pair's slice of out_mask and of out_errors' second axis;
+    None otherwise)."""
 
     def __init__(self):
         self.num_samples = self.num_candidates = 0
@@ -2267,12 +2367,14 @@ class RansacResult:
         self.model = None
         self.model_row = np.zeros(17)
         self.inlier_indices = [np.zeros(0, dtype=np.int32) for _ in range(3)]
+        self.num_inliers = (0, 0, 0)
+        self.rows = None
         self.norm_scale = 1.0
 
     def __repr__(self):
         return (f"RansacResult(index={self.index} of {self.num_candidates}, score {self.score_selected:.6g} -> "
                 f"{self.score_final:.6g}, rounds {self.rounds_accepted}/{self.rounds_run}, status={self.status}, "
-                f"inliers={[len(a) for a in self.inlier_indices]})")
+                f"inliers={list(self.num_inliers)})")
 
 
 def score_models(variant, x0, x1, depth0, depth1, cam0, cam1, options, est_config, models, with_errors=False,

@@ -693,6 +693,48 @@ int mp_residuals_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_
     });
 }
 
+int mp_ransac_out_set(mp_pair_set *set, const mp_draw_weights *handle, int32_t num_sel, const int32_t *pair_ids,
+                      int32_t budget, int32_t step, uint64_t seed, int32_t point_share, const int64_t *sample_offsets,
+                      const int32_t *sample_types, const int32_t *sample_idx, int32_t rounds, int32_t lo_rounds,
+                      int32_t lo_steps, int32_t weighted_stop, mp_model *models, mp_ransac_result *results,
+                      int32_t *inlier_idx, int32_t *stopped, mp_ransac_lo_info *lo_info,
+                      mp_ransac_lo_steps_info *steps_info, int64_t sample_chunk, int64_t model_chunk,
+                      mp_inlier_mass *rule_mass, const mp_ransac_out *out) {
+    return guarded([&]() {
+        static_assert(sizeof(mp_ransac_out) == 6 * sizeof(void *) && offsetof(mp_ransac_out, errors) == sizeof(void *) &&
+                          offsetof(mp_ransac_out, models) == 2 * sizeof(void *) &&
+                          offsetof(mp_ransac_out, index) == 3 * sizeof(void *) &&
+                          offsetof(mp_ransac_out, counts) == 4 * sizeof(void *) &&
+                          offsetof(mp_ransac_out, producer_stream) == 5 * sizeof(void *),
+                      "ransac out layout");
+        if (!set) throw std::invalid_argument("null pair set");
+        mp::RansacOut O;
+        if (out) {
+            O.mask = out->mask;
+            O.errors = out->errors;
+            O.models = out->models;
+            O.index = out->index;
+            O.counts = out->counts;
+            O.producer_stream = out->producer_stream;
+        }
+        mp::ransac_out_set(reinterpret_cast<mp::PairSet *>(set), reinterpret_cast<const mp::DrawWeights *>(handle),
+                           num_sel, pair_ids, budget, step, seed, point_share, sample_offsets, sample_types, sample_idx,
+                           rounds, lo_rounds, lo_steps, weighted_stop != 0, reinterpret_cast<mp::Model *>(models),
+                           reinterpret_cast<mp::RansacResult *>(results), inlier_idx, stopped,
+                           reinterpret_cast<mp::RansacLoInfo *>(lo_info),
+                           reinterpret_cast<mp::RansacLoStepsInfo *>(steps_info), sample_chunk, model_chunk,
+                           reinterpret_cast<mp::InlierMass *>(rule_mass), &O);
+        return MP_OK;
+    });
+}
+
+int mp_debug_ransac_out_stats(int64_t *launches, double *ms, int32_t reset) {
+    return guarded([&]() {
+        mp::ransac_out_stats(launches, ms, reset != 0);
+        return MP_OK;
+    });
+}
+
 int mp_debug_residuals_stats(int64_t *launches, double *ms, int32_t reset) {
     return guarded([&]() {
         mp::residuals_stats(launches, ms, reset != 0);

@@ -2620,9 +2620,11 @@ struct RefineBuffers {
 // m_init, LocalOptimization's first act, src/hybrid_ransac.h:383-411); its candidate is swept
 // over the relaxed lists' buffer, which are dead by then.  Everything else, the result's
 // tight counts and lists included, is as without.
+// swept (nullable; one per entry): the problem-unit model cur[j] the returned lists of entry j
+// were swept from, whether or not a round was accepted (mp_ransac_out_set evaluates it again).
 void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const int64_t *out_off,
                 const EstimatorConfig &cfg, int rounds, Model *models, RefineResult *results, int32_t *inlier_idx,
-                bool relax = false, double multiplier = 1.0, RefineBuffers *bufs = nullptr) {
+                bool relax = false, double multiplier = 1.0, RefineBuffers *bufs = nullptr, Model *swept = nullptr) {
     const int ns = sel.n;
     if (ns == 0) return;
     const int variant = R.variant, v = R.v;
@@ -2787,6 +2789,7 @@ void refine_run(ResidentPairs &R, hipStream_t stream, const PairSel sel, const i
             running.push_back(j);
         }
     }
+    for (int j = 0; swept && j < ns; ++j) swept[j] = cur[j];
     // ---- results: models back in user units, the accepted models' lists ----
     for (int j = 0; j < ns; ++j) {
         if (results[j].rounds_accepted == 0) continue; // (the given model, untouched)
@@ -4421,9 +4424,23 @@ void draw_plan(const ResidentPairs &R, const PairSel sel, const int32_t *first, 
 // The last stage of ransac_set and ransac_adaptive_set: the entries with a winner
 // (best_candidate >= 0, models[j] the winner) go through one refine_run, their lists to their
 // places in the selection; rounds = 0: nothing.
+// swept (nullable; one per entry of the selection): for the entries with a winner, the
+// problem-unit model their returned lists were swept from -- refine_run's, or with rounds = 0 the
+// selected candidate with its focals divided by norm_scale, as select_run divides them.
 void refine_winners(PairSet *set, hipStream_t stream, const PairSel sel, int32_t rounds, Model *models,
-                    RansacResult *results, int32_t *inlier_idx) {
-    if (rounds < 1) return;
+                    RansacResult *results, int32_t *inlier_idx, Model *swept = nullptr) {
+    if (rounds < 1) {
+        const ResidentPairs &R = *set->R;
+        for (int j = 0; swept && j < sel.n; ++j) {
+            if (results[j].best_candidate < 0) continue;
+            swept[j] = models[j];
+            if (R.variant == kSF || R.variant == kTF) {
+                swept[j].focal0 /= R.norm_scale[sel[j]];
+                swept[j].focal1 /= R.norm_scale[sel[j]];
+            }
+        }
+        return;
+    }
     std::vector<int32_t> win_ids;
     std::vector<int> win_j;
     std::vector<int64_t> win_off;
@@ -4438,11 +4455,13 @@ void refine_winners(PairSet *set, hipStream_t stream, const PairSel sel, int32_t
     if (win_j.empty()) return;
     const int nw = (int)win_j.size();
     std::vector<RefineResult> rres((size_t)nw);
+    std::vector<Model> win_swept(swept ? (size_t)nw : 0);
     refine_run(*set->R, stream, PairSel{nw, win_ids.data()}, win_off.data(), set->cfg, rounds, win_models.data(),
-               rres.data(), inlier_idx);
+               rres.data(), inlier_idx, false, 1.0, nullptr, swept ? win_swept.data() : nullptr);
     for (int i = 0; i < nw; ++i) {
         RansacResult &Q = results[win_j[(size_t)i]];
         const RefineResult &F = rres[(size_t)i];
+        if (swept) swept[win_j[(size_t)i]] = win_swept[(size_t)i];
         models[win_j[(size_t)i]] = win_models[(size_t)i];
         Q.score_initial = F.score_initial;
         Q.score_final = F.score_final;
@@ -4821,6 +4840,179 @@ void residuals_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, c
     g_resid_ms += ms;
 }
 
+// ---- ransac's results into the caller's device arrays (mp_ransac_out_set) ----
+namespace {
+std::mutex g_rout_mu;
+int64_t g_rout_launches = 0;
+double g_rout_ms = 0.0;
+
+// The output stage of the ransac bodies, under the set's mutex: check_args before anything,
+// begin once the selection is known and the context leased (every pointer check, then the
+// producer's event; nothing has been launched), swept() to refine_winners, finish after it.
+// Without outputs every step does nothing.
+struct RansacOutStage {
+    const RansacOut *out;
+    bool on = false;
+    int64_t rows = 0;
+    std::vector<Model> pm; // per entry: the problem-unit model its returned lists were swept from
+    hipEvent_t produced = nullptr;
+
+    explicit RansacOutStage(const RansacOut *o) : out(o && o->any() ? o : nullptr) {}
+    RansacOutStage(const RansacOutStage &) = delete;
+    RansacOutStage &operator=(const RansacOutStage &) = delete;
+    ~RansacOutStage() {
+        if (produced) (void)hipEventDestroy(produced);
+    }
+
+    void check_args(int32_t rounds, int32_t lo_rounds) const {
+        if (!out) return;
+        if (out->errors && !out->mask) throw std::invalid_argument("device array errors needs mask");
+        if (lo_rounds >= 1 && rounds == 0)
+            throw std::invalid_argument("device outputs with lo_rounds need rounds >= 1: without final rounds the "
+                                        "overall best's lists may be a local optimisation's, whose model in problem "
+                                        "units is not kept");
+    }
+
+    void begin(PairSet *set, int32_t num_sel, hipStream_t stream) {
+        if (!out) return;
+        rows = set->out_off[(size_t)num_sel];
+        static const char *const names[kRansacOutArrays] = {"mask", "errors", "models", "index", "counts"};
+        const int64_t elem[kRansacOutArrays] = {1, 8, 8, 4, 4};
+        const void *ptr[kRansacOutArrays] = {out->mask, out->errors, out->models, out->index, out->counts};
+        const int64_t bytes[kRansacOutArrays] = {resid_mask_bytes(rows), resid_error_bytes(rows),
+                                                 ransac_out_models_bytes(num_sel), ransac_out_index_bytes(num_sel),
+                                                 ransac_out_counts_bytes(num_sel)};
+        uint64_t addr[kRansacOutArrays];
+        for (int i = 0; i < kRansacOutArrays; ++i) {
+            addr[i] = bytes[i] == 0 ? 0 : (uint64_t)(uintptr_t)ptr[i]; // (no element: nothing is written)
+            if (addr[i]) check_device_array(names[i], ptr[i], bytes[i], elem[i], set->device);
+        }
+        int a = 0, b = 0;
+        if (ransac_out_overlap(addr, bytes, &a, &b))
+            throw std::invalid_argument(std::string("device arrays ") + names[a] + " and " + names[b] + " overlap");
+        // ---- the producer's work first: an event on its stream, no host wait ----
+        MP_HIP(hipEventCreateWithFlags(&produced, hipEventDisableTiming));
+        MP_HIP(hipEventRecord(produced, static_cast<hipStream_t>(out->producer_stream)));
+        MP_HIP(hipStreamWaitEvent(stream, produced, 0));
+        pm.assign((size_t)num_sel, Model{});
+        on = true;
+    }
+
+    Model *swept() { return on ? pm.data() : nullptr; }
+
+    void finish(PairSet *set, const PairSel sel, hipStream_t stream, const Model *models, const RansacResult *results) {
+        if (!on) return;
+        static_assert(sizeof(Model) == 17 * sizeof(double) && sizeof(RansacOutPair) == 152, "per-pair row layout");
+        const int32_t ns = sel.n;
+        ResidentPairs &R = *set->R;
+        const int64_t *row_off = set->out_off.data();
+        std::vector<int32_t> pairs((size_t)ns);
+        std::vector<unsigned char> winner((size_t)ns);
+        for (int32_t j = 0; j < ns; ++j) {
+            pairs[(size_t)j] = sel[j];
+            winner[(size_t)j] = results[j].best_candidate >= 0 ? 1 : 0;
+        }
+        // ---- the per-pair rows: one small launch from an uploaded record per entry ----
+        std::unique_ptr<DevArray<RansacOutPair>> d_rows;
+        std::vector<RansacOutPair> h_rows;
+        if (out->models || out->index || out->counts) {
+            h_rows.resize((size_t)ns);
+            for (int32_t j = 0; j < ns; ++j)
+                h_rows[(size_t)j] = ransac_out_pair(winner[(size_t)j] != 0, reinterpret_cast<const double *>(&models[j]),
+                                                    results[j].best_candidate, results[j].num_inliers);
+            d_rows.reset(new DevArray<RansacOutPair>((size_t)ns));
+            MP_HIP(hipMemcpyAsync(d_rows->p, h_rows.data(), sizeof(RansacOutPair) * (size_t)ns, hipMemcpyHostToDevice,
+                                  stream));
+            MP_HIP(launch_ransac_out_pairs(stream, d_rows->p, ns, static_cast<double *>(out->models),
+                                           static_cast<int *>(out->index), static_cast<int *>(out->counts)));
+        }
+        // ---- the rows: the runs and items of host/residuals_plan.h, written in place ----
+        int64_t launches = 0;
+        double ms = 0.0;
+        if (out->mask && rows > 0) {
+            struct Event {
+                hipEvent_t ev = nullptr;
+                ~Event() {
+                    if (ev) (void)hipEventDestroy(ev);
+                }
+            } t0, t1;
+            const bool timed = g_prof_on.load();
+            if (timed) {
+                MP_HIP(hipEventCreate(&t0.ev));
+                MP_HIP(hipEventCreate(&t1.ev));
+            }
+            const int64_t run_rows =
+                env_int("MADPOSE_RESIDUALS_RUN_ROWS", kResidRunRowsDevice, 1, kResidRunRowsDevice);
+            const int32_t run_entries =
+                (int32_t)env_int("MADPOSE_RESIDUALS_RUN_ENTRIES", kResidRunEntries, 1, kResidRunEntries);
+            std::vector<ResidRun> runs;
+            resid_runs(ns, row_off, run_rows, run_entries, runs);
+            size_t max_e = 0, max_items = 0;
+            for (const ResidRun &r : runs) {
+                max_e = std::max(max_e, (size_t)(r.e1 - r.e0));
+                max_items = std::max(max_items, (size_t)(r.e1 - r.e0) + (size_t)(r.rows / kResidItemRows));
+            }
+            DevArray<ScoreRec> d_recs(max_e);
+            DevArray<ResidItem> d_items(max_items);
+            DevArray<ResidCount> d_cnt(max_items);
+            std::vector<ScoreRec> recs;
+            std::vector<ResidItem> items;
+            std::vector<int64_t> first_item;
+            std::vector<ResidCount> cnt;
+            for (const ResidRun &r : runs) {
+                if (r.rows == 0) continue; // (pairs without correspondences: no row to write)
+                recs.assign((size_t)(r.e1 - r.e0), ScoreRec{});
+                for (int32_t e = r.e0; e < r.e1; ++e)
+                    if (winner[(size_t)e])
+                        prepare_score_rec(R.Ch[(size_t)pairs[(size_t)e]], pm[(size_t)e], recs[(size_t)(e - r.e0)]);
+                ransac_out_items(r, pairs.data(), winner.data(), row_off, items, first_item);
+                if (items.size() > max_items) throw std::logic_error("ransac_out: more items than planned");
+                cnt.resize(items.size());
+                MP_HIP(hipMemcpyAsync(d_recs.p, recs.data(), sizeof(ScoreRec) * recs.size(), hipMemcpyHostToDevice,
+                                      stream));
+                MP_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(ResidItem) * items.size(), hipMemcpyHostToDevice,
+                                      stream));
+                if (timed) MP_HIP(hipEventRecord(t0.ev, stream));
+                MP_HIP(launch_ransac_out(stream, R.v, R.d_D.p, R.d_C.p, d_items.p, (int)items.size(), d_recs.p,
+                                         static_cast<unsigned char *>(out->mask), static_cast<double *>(out->errors),
+                                         rows, d_cnt.p));
+                if (timed) MP_HIP(hipEventRecord(t1.ev, stream));
+                MP_HIP(hipMemcpyAsync(cnt.data(), d_cnt.p, sizeof(ResidCount) * items.size(), hipMemcpyDeviceToHost,
+                                      stream));
+                MP_HIP(hipStreamSynchronize(stream)); // (recs and items are reused by the next run)
+                if (timed) {
+                    float f = 0.f;
+                    MP_HIP(hipEventElapsedTime(&f, t0.ev, t1.ev));
+                    ms += f;
+                }
+                ++launches;
+                // the mask's counts are the returned lists' lengths, or the evaluation is not the sweep's
+                for (int32_t e = r.e0; e < r.e1; ++e) {
+                    int64_t sum[3] = {0, 0, 0};
+                    for (int64_t j = first_item[(size_t)(e - r.e0)]; j < first_item[(size_t)(e - r.e0) + 1]; ++j)
+                        for (int t = 0; t < 3; ++t) sum[t] += cnt[(size_t)j].count[t];
+                    for (int t = 0; t < 3; ++t)
+                        if (sum[t] != (winner[(size_t)e] ? results[e].num_inliers[t] : 0))
+                            throw std::logic_error("ransac_out: the mask of pair " + std::to_string(pairs[(size_t)e]) +
+                                                   " counts other rows than its lists hold");
+                }
+            }
+        }
+        MP_HIP(hipStreamSynchronize(stream));
+        std::lock_guard<std::mutex> sl(g_rout_mu);
+        g_rout_launches += launches;
+        g_rout_ms += ms;
+    }
+};
+} // namespace
+
+void ransac_out_stats(int64_t *launches, double *ms, bool reset) {
+    std::lock_guard<std::mutex> lk(g_rout_mu);
+    if (launches) *launches = g_rout_launches;
+    if (ms) *ms = g_rout_ms;
+    if (reset) g_rout_launches = 0, g_rout_ms = 0.0;
+}
+
 RansacTiming ransac_timing_last() {
     std::lock_guard<std::mutex> lk(g_ransac_mu);
     return g_ransac_timing;
@@ -4952,8 +5144,10 @@ void candidates_fetch(PairSet *set, Model *models, int64_t *model_offsets, int32
 void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
                 int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
                 const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
-                int64_t sample_chunk, int64_t model_chunk, const DrawWeights *weights) {
+                int64_t sample_chunk, int64_t model_chunk, const DrawWeights *weights, const RansacOut *out) {
     if (!set) throw std::invalid_argument("null pair set");
+    RansacOutStage stage(out);
+    stage.check_args(rounds, 0);
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
     if (model_chunk < 0) throw std::invalid_argument("model_chunk must not be negative");
@@ -4996,6 +5190,7 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
     const int64_t S = soff[num_sel] - soff[0];
     CtxLease lease(set->device);
     hipStream_t stream = lease.c->stream;
+    stage.begin(set, num_sel, stream);
 
     // ---- draw -> hypothesize -> compact ----
     HypCompact co;
@@ -5021,8 +5216,10 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
     t0 = Clock::now();
     std::vector<SelectResult> sres((size_t)num_sel);
     const int tile_set = g_select_tile.load();
+    // (mp_ransac_out_set, out not null: with a refinement to come the winners' lists are refine_run's)
     select_run(R, stream, sel, set->out_off.data(), cp.moff.data(), co.models.data(), nullptr, nullptr, sres.data(),
-               inlier_idx, model_chunk, tile_set ? tile_set : kSelectTile, timed, rt.select);
+               out && rounds >= 1 ? nullptr : inlier_idx, model_chunk, tile_set ? tile_set : kSelectTile, timed,
+               rt.select);
     rt.select_ms = 1e3 * secs(t0);
     for (int j = 0; j < num_sel; ++j) {
         RansacResult &Q = results[j];
@@ -5045,8 +5242,9 @@ void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t 
 
     // ---- refine: the pairs with a winner, their lists to their places in the selection ----
     t0 = Clock::now();
-    refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
+    refine_winners(set, stream, sel, rounds, models, results, inlier_idx, stage.swept());
     rt.refine_ms = 1e3 * secs(t0);
+    stage.finish(set, sel, stream, models, results);
     rt.total_ms = 1e3 * secs(t_all);
     if (timed) {
         std::lock_guard<std::mutex> lk2(g_ransac_mu);
@@ -5103,8 +5301,11 @@ void select_argmin_direct(int32_t num_pairs, const int64_t *model_offsets, const
 void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
                          uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
                          int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk,
-                         const DrawWeights *weights, bool weighted_stop, InlierMass *rule_mass) {
+                         const DrawWeights *weights, bool weighted_stop, InlierMass *rule_mass,
+                         const RansacOut *out) {
     if (!set) throw std::invalid_argument("null pair set");
+    RansacOutStage stage(out);
+    stage.check_args(rounds, 0);
     if (weighted_stop && !weights) throw std::invalid_argument("weighted_stop needs draw weights");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (sample_chunk < 0) throw std::invalid_argument("sample_chunk must not be negative");
@@ -5149,6 +5350,7 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     }
     CtxLease lease(set->device);
     hipStream_t stream = lease.c->stream;
+    stage.begin(set, num_sel, stream);
     RuleMass rule; // (weighted_stop: what the rule reads, host/ransac_stop.h required_samples_mass)
     if (weighted_stop) rule.init(R, sel, weights);
     if (!active.empty()) {
@@ -5240,7 +5442,8 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
     }
     if (weighted_stop && rule_mass) std::copy(rule.rm.begin(), rule.rm.end(), rule_mass);
     // ---- refine: once, the pairs with a winner ----
-    refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
+    refine_winners(set, stream, sel, rounds, models, results, inlier_idx, stage.swept());
+    stage.finish(set, sel, stream, models, results);
 }
 
 namespace {
@@ -5249,8 +5452,10 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
                    int64_t model_chunk, int32_t lo_steps, RansacLoStepsInfo *steps_info, const DrawWeights *weights,
-                   bool weighted_stop, InlierMass *rule_mass) {
+                   bool weighted_stop, InlierMass *rule_mass, const RansacOut *out) {
     if (!set) throw std::invalid_argument("null pair set");
+    RansacOutStage stage(out);
+    stage.check_args(rounds, 1);
     if (weighted_stop && !weights) throw std::invalid_argument("weighted_stop needs draw weights");
     if (rounds < 0 || rounds > 64) throw std::invalid_argument("rounds must be in 0..64");
     if (lo_rounds < 1 || lo_rounds > 64) throw std::invalid_argument("lo_rounds must be in 1..64");
@@ -5301,6 +5506,7 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
     }
     CtxLease lease(set->device);
     hipStream_t stream = lease.c->stream;
+    stage.begin(set, num_sel, stream);
     RuleMass rule; // (weighted_stop: what the rule reads, host/ransac_stop.h required_samples_mass)
     if (weighted_stop) rule.init(R, sel, weights);
     if (!active.empty()) {
@@ -5570,17 +5776,19 @@ void ransac_lo_run(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
         }
     }
     // ---- refine: once, the overall bests ----
-    refine_winners(set, stream, sel, rounds, models, results, inlier_idx);
+    refine_winners(set, stream, sel, rounds, models, results, inlier_idx, stage.swept());
+    stage.finish(set, sel, stream, models, results);
 }
 } // namespace
 
 void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step, uint64_t seed,
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
-                   int64_t model_chunk, const DrawWeights *weights, bool weighted_stop, InlierMass *rule_mass) {
+                   int64_t model_chunk, const DrawWeights *weights, bool weighted_stop, InlierMass *rule_mass,
+                   const RansacOut *out) {
     ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
                   inlier_idx, stopped, lo_info, sample_chunk, model_chunk, 0, nullptr, weights, weighted_stop,
-                  rule_mass);
+                  rule_mass, out);
 }
 
 void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, int32_t step,
@@ -5588,7 +5796,7 @@ void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
                          Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
                          RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
                          int64_t model_chunk, const DrawWeights *weights, bool weighted_stop,
-                         InlierMass *rule_mass) {
+                         InlierMass *rule_mass, const RansacOut *out) {
     if (!set) throw std::invalid_argument("null pair set");
     if (lo_steps < 1 || lo_steps > kLoStepsMax) throw std::invalid_argument("lo_steps must be in 1..64");
     if (num_sel > 0 && !steps_info) throw std::invalid_argument("null steps_info");
@@ -5598,7 +5806,43 @@ void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
         throw std::invalid_argument("threshold_multiplier must be positive and finite with lo_steps");
     ransac_lo_run(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
                   inlier_idx, stopped, lo_info, sample_chunk, model_chunk, lo_steps, steps_info, weights,
-                  weighted_stop, rule_mass);
+                  weighted_stop, rule_mass, out);
+}
+
+void ransac_out_set(PairSet *set, const DrawWeights *weights, int32_t num_sel, const int32_t *pair_ids, int32_t budget,
+                    int32_t step, uint64_t seed, int32_t point_share, const int64_t *sample_offsets,
+                    const int32_t *sample_types, const int32_t *sample_idx, int32_t rounds, int32_t lo_rounds,
+                    int32_t lo_steps, bool weighted_stop, Model *models, RansacResult *results, int32_t *inlier_idx,
+                    int32_t *stopped, RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
+                    int64_t model_chunk, InlierMass *rule_mass, const RansacOut *out) {
+    if (!set) throw std::invalid_argument("null pair set");
+    // (a body told apart from its own entry by out != null: the caller's, or one with nothing in it)
+    const RansacOut none;
+    const RansacOut *O = out ? out : &none;
+    RansacOutStage(O).check_args(rounds, lo_rounds); // (before the bodies' own checks: the refused combination)
+    if (step < 0) throw std::invalid_argument("step must be 0 (a fixed budget) or at least 1");
+    if (lo_rounds < 0 || lo_steps < 0) throw std::invalid_argument("lo_rounds and lo_steps must not be negative");
+    if (step == 0 && (lo_rounds != 0 || lo_steps != 0))
+        throw std::invalid_argument("lo_rounds and lo_steps need step: they run inside the adaptive rounds");
+    if (lo_rounds == 0 && lo_steps != 0) throw std::invalid_argument("lo_steps needs lo_rounds");
+    if (weighted_stop && !weights) throw std::invalid_argument("weighted_stop needs draw weights");
+    if (weighted_stop && step < 1)
+        throw std::invalid_argument("the weighted stop needs step >= 1: the rule is read at checkpoints");
+    const bool given = sample_offsets || sample_types || sample_idx;
+    if (given && step != 0) throw std::invalid_argument("given samples go with step 0: the adaptive rounds draw their own");
+    if (step == 0)
+        ransac_set(set, num_sel, pair_ids, budget, seed, point_share, sample_offsets, sample_types, sample_idx, rounds,
+                   models, results, inlier_idx, sample_chunk, model_chunk, weights, O);
+    else if (lo_rounds == 0)
+        ransac_adaptive_set(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, models, results, inlier_idx,
+                            stopped, sample_chunk, model_chunk, weights, weighted_stop, rule_mass, O);
+    else if (lo_steps == 0)
+        ransac_lo_set(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, models, results,
+                      inlier_idx, stopped, lo_info, sample_chunk, model_chunk, weights, weighted_stop, rule_mass, O);
+    else
+        ransac_lo_steps_set(set, num_sel, pair_ids, budget, step, seed, point_share, rounds, lo_rounds, lo_steps, models,
+                            results, inlier_idx, stopped, lo_info, steps_info, sample_chunk, model_chunk, weights,
+                            weighted_stop, rule_mass, O);
 }
 
 void ransac_lo_track(int32_t num_rounds, const double *min_score, const int32_t *min_counts, const int32_t *candidate,

@@ -348,10 +348,12 @@ void draw_host(int variant, int64_t n, uint64_t seed, int32_t point_share, int32
 int64_t candidates_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, const int64_t *sample_offsets,
                        const int32_t *sample_types, const int32_t *sample_idx, int64_t sample_chunk);
 void candidates_fetch(PairSet *set, Model *models, int64_t *model_offsets, int32_t *cand_sample, int32_t *cand_slot);
+struct RansacOut; // (below, at ransac_out_set)
 void ransac_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32_t budget, uint64_t seed,
                 int32_t point_share, const int64_t *sample_offsets, const int32_t *sample_types,
                 const int32_t *sample_idx, int32_t rounds, Model *models, RansacResult *results, int32_t *inlier_idx,
-                int64_t sample_chunk, int64_t model_chunk, const DrawWeights *weights = nullptr);
+                int64_t sample_chunk, int64_t model_chunk, const DrawWeights *weights = nullptr,
+                const RansacOut *out = nullptr);
 // The weight mass of models' inlier lists and the weighted stopping rule (mp_inlier_mass_set,
 // mp_ransac_weighted_stop_set; kernels/inlier_mass.h, host/ransac_stop.h required_samples_mass).
 // q_i = c[i + 1] - c[i] are the quantised confidences of the handle's table of the pair and
@@ -429,7 +431,7 @@ void ransac_adaptive_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
                          uint64_t seed, int32_t point_share, int32_t rounds, Model *models, RansacResult *results,
                          int32_t *inlier_idx, int32_t *stopped, int64_t sample_chunk, int64_t model_chunk,
                          const DrawWeights *weights = nullptr, bool weighted_stop = false,
-                         InlierMass *rule_mass = nullptr);
+                         InlierMass *rule_mass = nullptr, const RansacOut *out = nullptr);
 // ransac_lo_set (mp_ransac_lo_set): ransac_adaptive_set with the estimators' local
 // optimisation prefix inside the rounds, two tracks per pair.  The minimal track is
 // ransac_adaptive_set's in every bit (select_run is seeded with the minimal best's score).
@@ -456,7 +458,7 @@ void ransac_lo_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids, int32
                    int32_t point_share, int32_t rounds, int32_t lo_rounds, Model *models, RansacResult *results,
                    int32_t *inlier_idx, int32_t *stopped, RansacLoInfo *lo_info, int64_t sample_chunk,
                    int64_t model_chunk, const DrawWeights *weights = nullptr, bool weighted_stop = false,
-                   InlierMass *rule_mass = nullptr);
+                   InlierMass *rule_mass = nullptr, const RansacOut *out = nullptr);
 // ransac_lo_steps_set (mp_ransac_lo_steps_set): ransac_lo_set with the num_lo_steps steps of the
 // estimators' LocalOptimization after each local optimisation (host/ransac_lo_steps.h): lo_steps
 // steps per entry whose minimal best was replaced, from the model the relaxed refinement
@@ -473,7 +475,45 @@ void ransac_lo_steps_set(PairSet *set, int32_t num_sel, const int32_t *pair_ids,
                          Model *models, RansacResult *results, int32_t *inlier_idx, int32_t *stopped,
                          RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
                          int64_t model_chunk, const DrawWeights *weights = nullptr, bool weighted_stop = false,
-                         InlierMass *rule_mass = nullptr);
+                         InlierMass *rule_mass = nullptr, const RansacOut *out = nullptr);
+// ransac's results into the caller's device arrays (mp_ransac_out_set; kernels/ransac_out.h,
+// host/residuals_plan.h).  ransac_out_set takes the union of the arguments of the bodies above
+// and runs the one they choose (weights nullable; step 0: ransac_set, its samples given or drawn;
+// lo_rounds 0: ransac_adaptive_set; lo_steps 0: ransac_lo_set; else ransac_lo_steps_set), whose
+// results and bytes are the body's own.  inlier_idx null: no list is copied back from the device;
+// with a refinement to come the selection copies none either.  out (nullable; any subset of its
+// arrays): memory of the set's device for the selection's R = out_off[num_sel] rows and num_sel
+// pairs, checked before any launch as residuals_set checks its arrays, and pairwise disjoint.
+// For entry j with a winner: models[j] = the returned model's bytes, index[j] = best_candidate,
+// counts[j] = num_inliers; bit t of mask[out_off[j] + i] is set iff i is in the returned list t,
+// and errors[t R + out_off[j] + i] is the squared error, in problem units, under the model those
+// lists were swept from (refine_run's `swept`; rounds = 0: the selected candidate as select_run
+// converts it), so (errors[t] < thr_t) == bit t on every row.  Without a winner: zeros, index -1,
+// NaN errors.  Every element belonging to the selection is written once, by a kernel; the stage
+// adds its items' counts per pair and throws std::logic_error when they differ from num_inliers.
+// The library's stream waits for an event recorded on producer_stream before its first write.
+// std::invalid_argument before any launch: errors without mask; outputs with lo_rounds >= 1 and
+// rounds = 0 (the overall best's lists may be a local optimisation's, whose problem-unit model
+// is not kept); lo_rounds / lo_steps without step; lo_steps without lo_rounds; weighted_stop
+// without weights or step; samples with step or weights; and each body's own refusals.
+struct RansacOut {
+    void *mask = nullptr;    // uint8, R
+    void *errors = nullptr;  // float64, 3 R, term-major; needs mask
+    void *models = nullptr;  // float64, 17 num_sel
+    void *index = nullptr;   // int32, num_sel
+    void *counts = nullptr;  // int32, 3 num_sel
+    void *producer_stream = nullptr;
+    bool any() const { return mask || errors || models || index || counts; }
+};
+void ransac_out_set(PairSet *set, const DrawWeights *weights, int32_t num_sel, const int32_t *pair_ids, int32_t budget,
+                    int32_t step, uint64_t seed, int32_t point_share, const int64_t *sample_offsets,
+                    const int32_t *sample_types, const int32_t *sample_idx, int32_t rounds, int32_t lo_rounds,
+                    int32_t lo_steps, bool weighted_stop, Model *models, RansacResult *results, int32_t *inlier_idx,
+                    int32_t *stopped, RansacLoInfo *lo_info, RansacLoStepsInfo *steps_info, int64_t sample_chunk,
+                    int64_t model_chunk, InlierMass *rule_mass, const RansacOut *out);
+// ransac_out_stats (mp_debug_ransac_out_stats): the output stage's item launches since the last
+// reset and their summed device milliseconds (measured only while profiling is enabled).
+void ransac_out_stats(int64_t *launches, double *ms, bool reset);
 // Test hook (mp_debug_ransac_lo_track; no device): host/ransac_lo_track.h walked over
 // num_rounds rounds in each of which the minimal best was replaced (its score and counts,
 // its candidate index, and its LO's rounds_accepted, score_final and counts).  score: the

@@ -100,4 +100,58 @@ inline bool resid_overlap(uint64_t a, int64_t la, uint64_t b, int64_t lb) {
     return a <= b ? b - a < (uint64_t)la : a - b < (uint64_t)lb;
 }
 
+// ---- the output stage of mp_ransac_out_set (kernels/ransac_out.h) ----
+// Its entries are the selected pairs in selection order, each under at most one model: the
+// offsets, runs and items are the ones above (row_base 0: the caller's arrays hold the whole
+// call).  An entry without a winner keeps its items, marked as fill items: they store mask 0 and
+// NaN errors and read no record.  Every entry, also one without a correspondence (which has no
+// item), has one per-pair row: the model's 17 doubles, the winner's index and three counts.
+constexpr int kResidFill = -1; // ResidItem::rec of a fill item
+constexpr int kRansacOutArrays = 5;
+
+struct RansacOutPair {
+    double model[17];
+    int32_t index, count[3];
+};
+
+// resid_items for the output stage: winner[e] != 0 for the entries with a model
+inline void ransac_out_items(const ResidRun &r, const int32_t *pairs, const unsigned char *winner,
+                             const int64_t *row_off, std::vector<ResidItem> &items, std::vector<int64_t> &first_item) {
+    resid_items(r, pairs, nullptr, row_off, 0, items, first_item);
+    for (int32_t e = r.e0; e < r.e1; ++e) {
+        if (winner[e]) continue;
+        for (int64_t j = first_item[(size_t)(e - r.e0)]; j < first_item[(size_t)(e - r.e0) + 1]; ++j)
+            items[(size_t)j].rec = kResidFill;
+    }
+}
+
+// The per-pair row of an entry: the model's bytes, its index and its counts, or zeros, -1 and
+// zeros without a winner.
+inline RansacOutPair ransac_out_pair(bool winner, const double *model17, int32_t index, const int32_t *count) {
+    RansacOutPair p;
+    for (int i = 0; i < 17; ++i) p.model[i] = winner ? model17[i] : 0.0;
+    p.index = winner ? index : -1;
+    for (int t = 0; t < 3; ++t) p.count[t] = winner ? count[t] : 0;
+    return p;
+}
+
+// Bytes of the caller-owned per-pair outputs for ns entries; -1 when the count leaves int64
+inline int64_t ransac_out_models_bytes(int64_t ns) { return ingest_bytes(ns, 17, 8); }
+inline int64_t ransac_out_index_bytes(int64_t ns) { return ingest_bytes(ns, 1, 4); }
+inline int64_t ransac_out_counts_bytes(int64_t ns) { return ingest_bytes(ns, 3, 4); }
+
+// The first two of the kRansacOutArrays extents (address, bytes; a null address or bytes <= 0: not
+// given) that share a byte: their indices to *a < *b and true, or false.  Differences only.
+inline bool ransac_out_overlap(const uint64_t *addr, const int64_t *bytes, int *a, int *b) {
+    for (int i = 0; i < kRansacOutArrays; ++i)
+        for (int j = i + 1; j < kRansacOutArrays; ++j) {
+            if (!addr[i] || !addr[j]) continue;
+            if (resid_overlap(addr[i], bytes[i], addr[j], bytes[j])) {
+                *a = i, *b = j;
+                return true;
+            }
+        }
+    return false;
+}
+
 } // namespace mp

@@ -184,6 +184,17 @@ hipError_t launch_residuals(hipStream_t s, int variant, const PairData *Ds, cons
                             const ResidItem *items, int nitems, const ScoreRec *recs, unsigned char *mask,
                             double *errors, int64_t stride, ResidCount *out);
 
+// ransac's results into the caller's device arrays (ransac_out.h; mp_ransac_out_set).
+// launch_ransac_out: launch_residuals' items, rows and counts with the comparison err_t < thr_t
+// itself; an item with rec == kResidFill (a pair without a winner) stores mask 0 and NaN errors,
+// counts 0, and reads neither the pair nor a record.  launch_ransac_out_pairs: pairs[j] to row j
+// of models (17 doubles), index and counts (3 ints), each nullable.  Nothing else is written.
+hipError_t launch_ransac_out(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                             const ResidItem *items, int nitems, const ScoreRec *recs, unsigned char *mask,
+                             double *errors, int64_t stride, ResidCount *out);
+hipError_t launch_ransac_out_pairs(hipStream_t s, const RansacOutPair *pairs, int npairs, double *models, int *index,
+                                   int *counts);
+
 // Least-squares fits on random inlier subsets (lsq_subset.h; mp_lsq_fit_set).  One workgroup
 // per entry; entry k's model record is recs[k], its outcome out[k], its workspace slice ws +
 // entries[k].ws_off (6 * stride ints: the three wide lists, then the three subset lists, each
