@@ -947,6 +947,81 @@ int mp_residuals_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_
                      const mp_residuals_out *out, int64_t *row_offsets /* num_entries + 1 */,
                      int32_t *counts /* 3 * num_entries */);
 int mp_debug_residuals_stats(int64_t *launches /* nullable */, double *ms /* nullable */, int32_t reset);
+/* Per-entry information and covariance: how well a pair's correspondences determine a model.
+ * The entry is additive; the entries above and their bytes are unchanged.
+ *
+ * mp_information_set: entries, pair_ids, models and factors as mp_residuals_set takes them (a pair
+ * may occur in any number of entries; at most 2^24 entries; every variant 0 .. 3).  For entry e
+ * (model m on pair p), m goes to problem units as every set stage converts it.  Row i of the pair
+ * is a residual block of type t (0: depth-aware reprojection 0 -> 1, two residuals; 1: the same
+ * 1 -> 0, two residuals; 2: Sampson, one residual) iff bit t of mp_residuals_set's mask is set for
+ * it under factors[e].  The LO type gates block types as in the local optimisation (LO_type 1: no
+ * reprojection blocks, 2: no Sampson blocks), and use_shift, the scale-only rule and the Sampson
+ * weight are those of the job mp_refine_set would run on these lists.  With J the Jacobian of the
+ * remaining residuals r at m over the 11 parameters (rotation tangent 3, t 3, scale, offset0,
+ * offset1, focal0, focal1 -- the layout of mp_debug_lm_system), row e of the outputs is
+ *   H[66 e ..]    the packed upper triangle of J^T J, (a, b), a <= b, at 11 a - a (a - 1) / 2 + b - a;
+ *   g[11 e ..]    J^T r;
+ *   cost[e]       sum r^2 / 2;
+ *   cov[121 e ..] the inverse of H on the active parameters, row-major 11 x 11, zero on the rows
+ *                 and columns of inactive ones: with D_a = 1 / sqrt(H_aa), A = D H D is factored
+ *                 once by Cholesky and column k is D (A^-1 e_k) D_k from the two triangular solves;
+ * each array nullable (cov NULL skips the inverse's stores), and entries[e] (always host memory):
+ *   col[a]     1: parameter a is active (6 pose parameters whenever a block exists; scale with a
+ *              block of type 1; offset0 / offset1 with a block of type 0 / 1 and use_shift; the
+ *              focals the variant has);
+ *   status     1: at least one block after gating, else 0;
+ *   pd         1: the factorisation completed; 0: an active H_aa or a pivot was not positive and
+ *              finite (cov is all zero); -1: status 0 (H, g, cost, cov and col are all zero);
+ *   rows       2 (n0 + n1) + n2 over the gated block counts;
+ *   counts[t]  the rows with bit t set, before gating: mp_residuals_set's counts.
+ * Every entry of g and H that belongs to an inactive parameter is exactly 0.0.  A model with a NaN
+ * entry has no blocks.  pd = 1 says only that the factorisation completed: it does not detect an
+ * ill-conditioned system (with Sampson blocks alone |t| is a gauge and its pivot is rounding
+ * noise); gauges are not handled here.
+ *
+ * Units: everything is in problem units, like mp_residuals_set's errors.  Residuals are pixels
+ * for variants 0 and 3 and pixels / s for the focal variants, s the pair's normalization scale
+ * (mp_pair_set_norm_scales); a focal parameter is the user's focal / s.  So cov is the covariance
+ * under unit-variance residuals in those units; for a focal's row and column multiply by s per
+ * index (cov[f][f] by s * s), and the a-posteriori variance factor is 2 cost / (rows - n), n the
+ * number of active parameters.  The library does not multiply.
+ *
+ * Outputs: on_device 0 -- host arrays, filled through a device scratch in runs of bounded size.
+ * on_device 1 -- memory of the set's device, checked before any launch as mp_residuals_set checks
+ * its outputs (device memory of that device, aligned to 8 bytes, the bytes inside the allocation's
+ * address range, the given ranges pairwise disjoint); the finishing kernel writes row e of each
+ * directly and nothing else.  producer_stream and the return are mp_residuals_set's.  A result
+ * depends on its entry alone: not on the other entries, the runs, or the output kind.  The call
+ * leaves nothing in the set that a later call can see.
+ * MP_EINVAL, before the device is touched: a NULL set, out or entries (num_entries > 0); NULL
+ * models with num_entries > 0; num_entries negative or above 2^24; a pair outside the set;
+ * pair_ids NULL with num_entries != num_pairs; a factor that is not finite and > 0; device outputs
+ * that overlap.
+ * mp_debug_information_finish: the finishing arithmetic alone, on the host (no device): H and g
+ * are masked in place by col (exact zeros on inactive entries), cov = the inverse as above, *pd 1
+ * or 0.  mp_debug_information_stats: the stage's runs since the last reset and, measured while
+ * profiling is enabled, the summed device milliseconds of its two kernels. */
+typedef struct mp_information_out {
+    void *H;               /* nullable; float64, 66 per entry */
+    void *g;               /* nullable; float64, 11 per entry */
+    void *cost;            /* nullable; float64, 1 per entry */
+    void *cov;             /* nullable; float64, 121 per entry */
+    int32_t on_device;     /* 0: host arrays; 1: device memory of the set's device */
+    int32_t pad;
+    void *producer_stream; /* on_device only; NULL: the null stream */
+} mp_information_out;
+typedef struct mp_information_entry {
+    int32_t col[11];
+    int32_t pd, status, rows;
+    int32_t counts[3];
+} mp_information_entry;
+int mp_information_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_ids /* nullable: pair e */,
+                       const mp_model *models /* user units */, const double *factors /* nullable: 1.0 */,
+                       const mp_information_out *out, mp_information_entry *entries /* num_entries */);
+int mp_debug_information_finish(double H[66], double g[11], const int32_t col[11], double cov[121], int32_t *pd);
+int mp_debug_information_stats(int64_t *launches /* nullable */, double *rows_ms /* nullable */,
+                               double *finish_ms /* nullable */, int32_t reset);
 /* RANSAC results into the caller's device arrays.  The entry is additive; the six ransac entries
  * above and their bytes are unchanged.
  *

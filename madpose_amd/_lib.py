@@ -240,6 +240,31 @@ class mp_residuals_out(ctypes.Structure):
 RESIDUALS_MAX_ENTRIES = 1 << 24  # mp_residuals_set's entries per call
 
 
+class mp_information_out(ctypes.Structure):
+    _fields_ = [
+        ("H", ctypes.c_void_p),
+        ("g", ctypes.c_void_p),
+        ("cost", ctypes.c_void_p),
+        ("cov", ctypes.c_void_p),
+        ("on_device", ctypes.c_int32),
+        ("pad", ctypes.c_int32),
+        ("producer_stream", ctypes.c_void_p),
+    ]
+
+
+class mp_information_entry(ctypes.Structure):
+    _fields_ = [
+        ("col", ctypes.c_int32 * 11),
+        ("pd", ctypes.c_int32),
+        ("status", ctypes.c_int32),
+        ("rows", ctypes.c_int32),
+        ("counts", ctypes.c_int32 * 3),
+    ]
+
+
+INFORMATION_MAX_ENTRIES = 1 << 24  # mp_information_set's entries per call
+
+
 class mp_ransac_out(ctypes.Structure):
     _fields_ = [
         ("mask", ctypes.c_void_p),
@@ -365,6 +390,11 @@ EXPORTS = {
     "mp_residuals_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.POINTER(mp_model),
                                         c_double_p, ctypes.POINTER(mp_residuals_out), c_int64_p, c_int32_p]),
     "mp_debug_residuals_stats": (ctypes.c_int, [c_int64_p, c_double_p, ctypes.c_int32]),
+    "mp_information_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.POINTER(mp_model),
+                                          c_double_p, ctypes.POINTER(mp_information_out),
+                                          ctypes.POINTER(mp_information_entry)]),
+    "mp_debug_information_finish": (ctypes.c_int, [c_double_p, c_double_p, c_int32_p, c_double_p, c_int32_p]),
+    "mp_debug_information_stats": (ctypes.c_int, [c_int64_p, c_double_p, c_double_p, ctypes.c_int32]),
     "mp_ransac_out_set": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int32, c_int32_p, ctypes.c_int32,
                                          ctypes.c_int32, ctypes.c_uint64, ctypes.c_int32, c_int64_p, c_int32_p,
                                          c_int32_p, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,

@@ -1774,6 +1774,152 @@ class PairSet:
         res.offsets = row_offsets
         return res
 
+    def information(self, models, pair_ids=None, factor=1.0, covariance=True, out_H=None, out_g=None, out_cost=None,
+                    out_cov=None, stream=None):
+        """How well each pair's correspondences determine a model (mp_information_set): an
+        InformationResult with, per entry, the Gauss-Newton system of the estimators' cost over
+        the model's inliers and its inverse.
+
+        Entries as in residuals: models is a sequence of pose objects or an (ne, 17) float64
+        array in user units, pair_ids (None: all pairs in order) MAY repeat a pair, factor is a
+        scalar or one value per entry.  For entry e (model m on pair p), row i is a residual
+        block of type t iff bit t of residuals(m, factor) is set for it; LO_type 1 drops the
+        reprojection blocks and 2 the Sampson blocks, and use_shift, the scale-only rule and the
+        Sampson weight are those of the job refine would run on these lists.  In the layout
+        rotation tangent 3, t 3, scale, offset0, offset1, focal0, focal1: H[e] (66) is the
+        packed upper triangle of J^T J, g[e] (11) is J^T r, cost[e] = sum r^2 / 2, cov[e] (11,
+        11) the inverse of H on the active parameters col[e] (zero elsewhere), rows[e] = 2 (n0 +
+        n1) + n2 over the gated block counts and counts[e] residuals' counts.  status 1: at
+        least one block; pd 1: the Cholesky factorisation completed, 0: an active H_aa or a
+        pivot was not positive and finite (cov zero), -1: status 0, everything zero (a model
+        with a NaN entry, a pair without correspondences, no row inside the thresholds).  pd = 1
+        does not detect an ill-conditioned system: with Sampson blocks alone |t| is a gauge and
+        its variance is rounding noise; gauges are not handled.
+
+        Units: everything is in problem units, like residuals' errors -- residuals in pixels for
+        the calibrated variants and pixels / norm_scale[p] for the focal variants, whose focal
+        parameters are focal / norm_scale[p].  cov is the inverse of H under unit-variance
+        residuals: for a focal's row and column multiply by norm_scale[p] per index, and the
+        a-posteriori variance factor is 2 cost / (rows - n), n the number of active parameters.
+        InformationResult.covariance(e, scaled=True) does both on the host.
+
+        The results are host numpy arrays, or any subset of out_H (ne, 66), out_g (ne, 11),
+        out_cost (ne,) and out_cov (ne, 11, 11): float64, C-contiguous, writable, pairwise
+        disjoint and of one kind -- numpy arrays, or device arrays (__cuda_array_interface__,
+        e.g. torch tensors on the set's device) that the finishing kernel writes directly;
+        stream is then the stream they were last used on.  With host outputs, what is not given
+        as out_* is a new numpy array of the result; with device outputs only the given arrays
+        are computed and the others are None.  covariance=False without out_cov skips the
+        inverse's stores (cov is None; pd is still reported).  col, pd, status, rows and counts
+        always come back to the host.  ValueError, before any library call, for every malformed
+        argument."""
+        h = self._live()
+        P = len(self._sizes)
+        if isinstance(models, np.ndarray):
+            if models.dtype != np.float64 or models.ndim != 2 or models.shape[1] != 17:
+                raise ValueError(f"array models must be float64 of shape (ne, 17), got {models.dtype} {models.shape}")
+            ne = models.shape[0]
+        else:
+            try:
+                ne = len(models)
+            except TypeError:
+                raise ValueError("models must be a sequence of poses or an (ne, 17) float64 array") from None
+        if pair_ids is None:
+            if ne != P:
+                raise ValueError(f"one model per pair: {ne} for {P} pairs")
+            ptr = None
+            sizes = list(self._sizes)
+        else:
+            ids = np.ascontiguousarray(np.asarray(pair_ids, dtype=np.int64).reshape(-1))
+            if len(ids) != ne:
+                raise ValueError(f"one model per entry: {ne} for {len(ids)} pair_ids")
+            for j, k in enumerate(ids.tolist()):
+                if not 0 <= k < P:
+                    raise ValueError(f"pair_ids[{j}] = {k} is outside the set of {P} pairs")
+            ids = ids.astype(np.int32)
+            ptr = ids.ctypes.data_as(L.c_int32_p)
+            sizes = [self._sizes[k] for k in ids.tolist()]
+        if ne > L.INFORMATION_MAX_ENTRIES:
+            raise ValueError("at most 2^24 entries per call")
+        fa = np.asarray(factor)
+        if fa.dtype == np.bool_ or fa.dtype.kind not in "fiu":
+            raise ValueError("factor must be a number or one number per entry")
+        fa = np.ascontiguousarray(np.broadcast_to(fa, (ne,)) if fa.ndim == 0 else fa.reshape(-1), dtype=np.float64)
+        if len(fa) != ne:
+            raise ValueError(f"one factor value per entry: {len(fa)} for {ne}")
+        if not np.all(np.isfinite(fa) & (fa > 0)):
+            raise ValueError("factor must be finite and positive")
+        if not isinstance(covariance, (bool, np.bool_)):
+            raise ValueError("covariance must be True or False")
+        want_cov = bool(covariance) or out_cov is not None
+
+        shapes = (("out_H", out_H, (ne, 66)), ("out_g", out_g, (ne, 11)), ("out_cost", out_cost, (ne,)),
+                  ("out_cov", out_cov, (ne, 11, 11)))
+        kinds, given = set(), {}
+        for name, a, shape in shapes:
+            if a is None:
+                continue
+            kind, addr = _output_array(a, name, ("<f8", "=f8"), np.float64, shape, f"ne = {ne} entries")
+            kinds.add(kind)
+            given[name] = (addr, 8 * int(np.prod(shape, dtype=np.int64)))
+        if len(kinds) > 1:
+            raise ValueError("out_H, out_g, out_cost and out_cov must be of one kind: all numpy arrays or all device "
+                             "arrays")
+        names = sorted(given)
+        for i, a in enumerate(names):
+            for b in names[i + 1:]:
+                (pa, la), (pb, lb) = given[a], given[b]
+                if la > 0 and lb > 0 and pa < pb + lb and pb < pa + la:
+                    raise ValueError(f"{a} and {b} overlap")
+        on_device = "device" in kinds
+        producer = None
+        if stream is not None:
+            if not on_device:
+                raise ValueError("stream goes with device outputs")
+            handle = getattr(stream, "cuda_stream", stream)
+            if isinstance(handle, bool) or not isinstance(handle, int) or handle < 0:
+                raise ValueError("stream must be None, an integer stream handle or an object with .cuda_stream")
+            producer = handle or None
+        if isinstance(models, np.ndarray):
+            keep = np.ascontiguousarray(models)
+            arr = keep.ctypes.data_as(ctypes.POINTER(L.mp_model))
+        else:
+            keep = arr = (L.mp_model * max(ne, 1))(*[_model_to_c(m, self.variant) for m in models])
+
+        res = InformationResult()
+        res.H, res.g, res.cost = np.zeros((ne, 66)), np.zeros((ne, 11)), np.zeros(ne)
+        res.cov = np.zeros((ne, 11, 11)) if want_cov else None
+        res.col = np.zeros((ne, 11), dtype=np.int32)
+        res.pd = np.full(ne, -1, dtype=np.int32)
+        res.status = np.zeros(ne, dtype=np.int32)
+        res.rows = np.zeros(ne, dtype=np.int32)
+        res.counts = np.zeros((ne, 3), dtype=np.int32)
+        res.norm_scale = np.array([self._norm[k] for k in (range(P) if pair_ids is None else ids.tolist())],
+                                  dtype=np.float64).reshape(ne)
+        res.focal_columns = (9,) if self.variant == L.SHARED_FOCAL else ((9, 10) if self.variant == L.TWO_FOCAL else ())
+        for name, a, _ in shapes:  # (the caller's arrays are the result's; device outputs: no others)
+            if a is not None or on_device:
+                setattr(res, name[4:], a)
+        if ne == 0 or (sum(sizes) == 0 and not on_device):  # (answered here: nothing to launch)
+            for a in (res.H, res.g, res.cost, res.cov):
+                if a is not None:
+                    a[...] = 0.0
+            return res
+        ent = (L.mp_information_entry * ne)()
+        out = L.mp_information_out()
+        for name, _, _ in shapes:
+            a = getattr(res, name[4:])
+            setattr(out, name[4:], None if a is None else (given[name][0] if on_device else a.ctypes.data))
+        out.on_device = 1 if on_device else 0
+        out.producer_stream = producer
+        L.check(L.lib().mp_information_set(h, ne, ptr, arr, _dp(fa), ctypes.byref(out), ent))
+        del keep
+        rec = np.frombuffer(ent, dtype=np.int32).reshape(ne, 17)
+        res.col[...] = rec[:, 0:11]
+        res.pd[...], res.status[...], res.rows[...] = rec[:, 11], rec[:, 12], rec[:, 13]
+        res.counts[...] = rec[:, 14:17]
+        return res
+
     def _check_draw(self, budget, seed, point_share, ns):
         if isinstance(budget, bool) or not isinstance(budget, (int, np.integer)) or budget < 0:
             raise ValueError("budget must be a non-negative integer")
@@ -2308,6 +2454,80 @@ class ResidualsResult:
 
     def __repr__(self):
         return f"ResidualsResult(entries={len(self.counts)}, rows={int(self.offsets[-1])})"
+
+
+INFORMATION_PARAMETERS = ("rot0", "rot1", "rot2", "t0", "t1", "t2", "scale", "offset0", "offset1", "focal0", "focal1")
+
+
+class InformationResult:
+    """PairSet.information's outcome, one row per entry, in problem units and in the layout of
+    INFORMATION_PARAMETERS: H ((ne, 66) packed upper triangle of J^T J), g ((ne, 11) J^T r), cost
+    ((ne,) sum r^2 / 2), cov ((ne, 11, 11) the inverse of H on the active parameters, or None when
+    not asked for) -- numpy arrays, or the objects passed as out_* -- and, always numpy: col ((ne,
+    11) the active mask), pd (1 inverted, 0 not positive definite, -1 nothing evaluated), status
+    (1: at least one block), rows (2 (n0 + n1) + n2 after gating), counts ((ne, 3) residuals'
+    counts), norm_scale (the entry's pair's) and focal_columns (the variant's focal parameters)."""
+
+    def __init__(self):
+        self.H = self.g = self.cost = self.cov = None
+        self.col = self.pd = self.status = self.rows = self.counts = None
+        self.norm_scale = None
+        self.focal_columns = ()
+
+    @staticmethod
+    def _host(a, name):
+        if not isinstance(a, np.ndarray):
+            raise ValueError(f"{name} is not a host array of this result"
+                             + ("" if a is None else ": copy the device array to the host first"))
+        return a
+
+    def active(self, e):
+        """The indices of entry e's active parameters."""
+        return np.flatnonzero(self.col[e])
+
+    def matrix(self, e):
+        """The full symmetric 11 x 11 H of entry e."""
+        Hp = self._host(self.H, "H")[e]
+        M = np.zeros((11, 11))
+        M[np.triu_indices(11)] = Hp
+        return M + np.triu(M, 1).T
+
+    def covariance(self, e, scaled=True):
+        """The covariance of entry e's active parameters (in active(e)'s order), symmetrised
+        (C + C^T) / 2.  scaled: in user units and with the a-posteriori variance factor -- a
+        focal's row and column times norm_scale per index, everything times 2 cost / (rows -
+        n); scaled=False: the inverse of H in problem units.  ValueError when the inverse was
+        not formed (pd != 1) or, with scaled, rows <= n."""
+        C = self._host(self.cov, "cov")[e]
+        if self.pd[e] != 1:
+            raise ValueError(f"entry {e} has no covariance: pd = {int(self.pd[e])}")
+        act = self.active(e)
+        n = len(act)
+        C = C[np.ix_(act, act)]
+        C = (C + C.T) / 2
+        if scaled:
+            if self.rows[e] <= n:
+                raise ValueError(f"entry {e} has {int(self.rows[e])} rows for {n} parameters: no variance factor")
+            s = np.array([self.norm_scale[e] if a in self.focal_columns else 1.0 for a in act])
+            C = C * np.outer(s, s) * (2.0 * float(self._host(self.cost, "cost")[e]) / (int(self.rows[e]) - n))
+        return C
+
+    def __repr__(self):
+        return f"InformationResult(entries={len(self.pd)})"
+
+
+def information_finish(H, g, col):
+    """The finishing arithmetic of PairSet.information on the host -- test hook
+    (mp_debug_information_finish; no device): (H, g, cov, pd) with H (66) and g (11) masked by
+    col (11) and cov (11, 11) the inverse on the active set, pd 1 or 0."""
+    H = np.array(H, dtype=np.float64).reshape(66)
+    g = np.array(g, dtype=np.float64).reshape(11)
+    c = np.ascontiguousarray(np.asarray(col).reshape(11) != 0, dtype=np.int32)
+    cov = np.zeros((11, 11))
+    pd = ctypes.c_int32(-2)
+    L.check(L.lib().mp_debug_information_finish(_dp(H), _dp(g), c.ctypes.data_as(L.c_int32_p), _dp(cov),
+                                                ctypes.byref(pd)))
+    return H, g, cov, int(pd.value)
 
 
 class LsqFitResult:

@@ -11,6 +11,7 @@
 #include "host/engine.h"
 #include "include/mp_subset.h"
 #include "host/hypothesis_plan.h"
+#include "host/information_plan.h"
 #include "host/ingest_plan.h"
 #include "host/pair_set_plan.h"
 #include "host/rng.h"
@@ -738,6 +739,49 @@ int mp_debug_ransac_out_stats(int64_t *launches, double *ms, int32_t reset) {
 int mp_debug_residuals_stats(int64_t *launches, double *ms, int32_t reset) {
     return guarded([&]() {
         mp::residuals_stats(launches, ms, reset != 0);
+        return MP_OK;
+    });
+}
+
+int mp_information_set(mp_pair_set *set, int32_t num_entries, const int32_t *pair_ids, const mp_model *models,
+                       const double *factors, const mp_information_out *out, mp_information_entry *entries) {
+    return guarded([&]() {
+        static_assert(sizeof(mp_information_entry) == sizeof(mp::InfoRecord) &&
+                          offsetof(mp_information_entry, pd) == offsetof(mp::InfoRecord, pd) &&
+                          offsetof(mp_information_entry, status) == offsetof(mp::InfoRecord, status) &&
+                          offsetof(mp_information_entry, rows) == offsetof(mp::InfoRecord, rows) &&
+                          offsetof(mp_information_entry, counts) == offsetof(mp::InfoRecord, counts),
+                      "information entry layout");
+        if (!set) throw std::invalid_argument("null pair set");
+        if (!out) throw std::invalid_argument("null out");
+        mp::InformationOut O;
+        O.H = out->H;
+        O.g = out->g;
+        O.cost = out->cost;
+        O.cov = out->cov;
+        O.on_device = out->on_device;
+        O.producer_stream = out->producer_stream;
+        mp::information_set(reinterpret_cast<mp::PairSet *>(set), num_entries, pair_ids,
+                            reinterpret_cast<const mp::Model *>(models), factors, O,
+                            reinterpret_cast<mp::InfoRecord *>(entries));
+        return MP_OK;
+    });
+}
+
+int mp_debug_information_finish(double H[66], double g[11], const int32_t col[11], double cov[121], int32_t *pd) {
+    return guarded([&]() {
+        if (!H || !g || !col || !cov || !pd) throw std::invalid_argument("null argument");
+        int c[mp::kInfoN];
+        for (int a = 0; a < mp::kInfoN; ++a) c[a] = col[a] != 0 ? 1 : 0;
+        mp::info_mask(H, g, c);
+        *pd = mp::info_covariance(H, c, cov);
+        return MP_OK;
+    });
+}
+
+int mp_debug_information_stats(int64_t *launches, double *rows_ms, double *finish_ms, int32_t reset) {
+    return guarded([&]() {
+        mp::information_stats(launches, rows_ms, finish_ms, reset != 0);
         return MP_OK;
     });
 }

@@ -4840,6 +4840,187 @@ void residuals_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, c
     g_resid_ms += ms;
 }
 
+// ---- the Gauss-Newton system over a model's inliers and its inverse (mp_information_set) ----
+namespace {
+std::mutex g_info_mu;
+int64_t g_info_launches = 0;
+double g_info_rows_ms = 0.0, g_info_finish_ms = 0.0;
+} // namespace
+
+void information_stats(int64_t *launches, double *rows_ms, double *finish_ms, bool reset) {
+    std::lock_guard<std::mutex> lk(g_info_mu);
+    if (launches) *launches = g_info_launches;
+    if (rows_ms) *rows_ms = g_info_rows_ms;
+    if (finish_ms) *finish_ms = g_info_finish_ms;
+    if (reset) g_info_launches = 0, g_info_rows_ms = g_info_finish_ms = 0.0;
+}
+
+void information_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, const Model *models,
+                     const double *factors, const InformationOut &out, InfoRecord *entries) {
+    static_assert(sizeof(Model) == 17 * sizeof(double), "InfoJob::m");
+    if (!set) throw std::invalid_argument("null pair set");
+    if (num_entries < 0 || num_entries > kInfoEntriesMax) throw std::invalid_argument("num_entries must be in 0..2^24");
+    if (num_entries > 0 && !entries) throw std::invalid_argument("null entries");
+    std::lock_guard<std::mutex> lk(set->mu);
+    residuals_check(set, num_entries, pair_ids, models, factors);
+    if (num_entries == 0) return;
+    const int32_t ne = num_entries;
+    ResidentPairs &R = *set->R;
+    const int variant = R.variant;
+    std::vector<int32_t> pairs((size_t)ne);
+    std::vector<int64_t> sizes((size_t)ne), row_off((size_t)ne + 1);
+    for (int32_t e = 0; e < ne; ++e) {
+        pairs[(size_t)e] = pair_ids ? pair_ids[e] : e;
+        sizes[(size_t)e] = R.n[(size_t)pairs[(size_t)e]];
+    }
+    resid_offsets(ne, sizes.data(), row_off.data());
+    const int64_t rows = row_off[(size_t)ne];
+    const bool dev = out.on_device != 0;
+    static const char *const names[kInfoArrays] = {"H", "g", "cost", "cov"};
+    const int64_t per[kInfoArrays] = {kInfoPack, kInfoN, 1, kInfoN * kInfoN};
+    void *const ptr[kInfoArrays] = {out.H, out.g, out.cost, out.cov};
+    const int64_t bytes[kInfoArrays] = {info_H_bytes(ne), info_g_bytes(ne), info_cost_bytes(ne), info_cov_bytes(ne)};
+    {
+        // the outputs' extents, host or device: differences only, before anything is written
+        uint64_t addr[kInfoArrays];
+        for (int i = 0; i < kInfoArrays; ++i) {
+            addr[i] = (uint64_t)(uintptr_t)ptr[i];
+            if (addr[i] && bytes[i] < 0) throw std::invalid_argument(std::string("array ") + names[i] + " leaves int64");
+        }
+        int a = 0, b = 0;
+        if (info_out_overlap(addr, bytes, &a, &b))
+            throw std::invalid_argument(std::string(dev ? "device arrays " : "arrays ") + names[a] + " and " +
+                                        names[b] + " overlap");
+    }
+    InfoRecord none;
+    std::memset(&none, 0, sizeof(none));
+    none.pd = -1;
+    std::fill(entries, entries + ne, none);
+    if (rows == 0 && !dev) { // (no row: nothing is launched; every entry is status 0)
+        for (int i = 0; i < kInfoArrays; ++i)
+            if (ptr[i]) std::memset(ptr[i], 0, (size_t)bytes[i]);
+        return;
+    }
+
+    CtxLease lease(set->device);
+    hipStream_t stream = lease.c->stream;
+    struct Event { // (destroyed after the last synchronise, or on the way out)
+        hipEvent_t ev = nullptr;
+        ~Event() {
+            if (ev) (void)hipEventDestroy(ev);
+        }
+    } produced, t0, t1, t2;
+    if (dev) {
+        // ---- every device pointer, before any launch or copy ----
+        for (int i = 0; i < kInfoArrays; ++i)
+            if (ptr[i]) check_device_array(names[i], ptr[i], bytes[i], 8, set->device);
+        // ---- the producer's work first: an event on its stream, no host wait ----
+        MP_HIP(hipEventCreateWithFlags(&produced.ev, hipEventDisableTiming));
+        MP_HIP(hipEventRecord(produced.ev, static_cast<hipStream_t>(out.producer_stream)));
+        MP_HIP(hipStreamWaitEvent(stream, produced.ev, 0));
+        if (rows == 0) { // (no row: no kernel; the entries' rows of the outputs are zero)
+            for (int i = 0; i < kInfoArrays; ++i)
+                if (ptr[i]) MP_HIP(hipMemsetAsync(ptr[i], 0, (size_t)bytes[i], stream));
+            MP_HIP(hipStreamSynchronize(stream));
+            return;
+        }
+    }
+    const bool timed = g_prof_on.load();
+    if (timed) {
+        MP_HIP(hipEventCreate(&t0.ev));
+        MP_HIP(hipEventCreate(&t1.ev));
+        MP_HIP(hipEventCreate(&t2.ev));
+    }
+
+    // (MADPOSE_INFORMATION_RUN_ROWS / _RUN_ENTRIES: smaller runs, for the tests of the cut)
+    const int64_t run_rows = env_int("MADPOSE_INFORMATION_RUN_ROWS", kInfoRunRows, 1, kInfoRunRows);
+    const int32_t run_entries = (int32_t)env_int("MADPOSE_INFORMATION_RUN_ENTRIES", kInfoRunEntries, 1, kInfoRunEntries);
+    std::vector<ResidRun> runs;
+    resid_runs(ne, row_off.data(), run_rows, run_entries, runs);
+    size_t max_e = 0;
+    int64_t max_items = 0;
+    for (const ResidRun &r : runs) {
+        max_e = std::max(max_e, (size_t)(r.e1 - r.e0));
+        max_items = std::max(max_items, info_max_items(r));
+    }
+    if (info_workspace_bytes(max_items) < 0) throw std::invalid_argument("information: the workspace leaves int64");
+    DevArray<ScoreRec> d_recs(max_e);
+    DevArray<InfoJob> d_jobs(max_e);
+    DevArray<InfoRecord> d_out(max_e);
+    DevArray<ResidItem> d_items((size_t)std::max<int64_t>(max_items, 1));
+    DevArray<InfoPartial> d_part((size_t)std::max<int64_t>(max_items, 1));
+    // host outputs: the scratch of one run (device outputs are written in place)
+    std::unique_ptr<DevArray<double>> d_scr[kInfoArrays];
+    for (int i = 0; i < kInfoArrays && !dev; ++i)
+        if (ptr[i]) d_scr[i].reset(new DevArray<double>((size_t)per[i] * max_e));
+    std::vector<ScoreRec> recs;
+    std::vector<InfoJob> jobs;
+    std::vector<ResidItem> items;
+    std::vector<int64_t> first_item;
+    const int one[3] = {1, 1, 1};
+    int64_t launches = 0;
+    double rows_ms = 0.0, finish_ms = 0.0;
+    for (const ResidRun &r : runs) {
+        const size_t nr = (size_t)(r.e1 - r.e0);
+        recs.resize(nr);
+        jobs.resize(nr);
+        resid_items(r, pairs.data(), factors, row_off.data(), r.row0, items, first_item);
+        if ((int64_t)items.size() > max_items) throw std::logic_error("information: more items than planned");
+        for (int32_t e = r.e0; e < r.e1; ++e) {
+            const int k = pairs[(size_t)e];
+            Model c = models[e];
+            if (variant == kSF || variant == kTF) {
+                c.focal0 /= R.norm_scale[(size_t)k];
+                c.focal1 /= R.norm_scale[(size_t)k];
+            }
+            prepare_score_rec(R.Ch[(size_t)k], c, recs[(size_t)(e - r.e0)]);
+            // the flags of the job refine would run on these lists (sizes 1: what the LO type leaves)
+            const LmJob L = make_lm_job(R.Ps[(size_t)k], set->cfg, one, 0, false, c);
+            InfoJob &J = jobs[(size_t)(e - r.e0)];
+            std::memcpy(J.m, &c, sizeof(J.m));
+            J.w_sampson = L.w_sampson;
+            J.use_reproj = L.n0 > 0 ? 1 : 0;
+            J.use_sampson = L.n2 > 0 ? 1 : 0;
+            J.use_shift = L.use_shift;
+            J.first_item = first_item[(size_t)(e - r.e0)];
+            J.nitems = (int)(first_item[(size_t)(e - r.e0) + 1] - J.first_item);
+            J.out_row = dev ? (int64_t)e : (int64_t)(e - r.e0);
+        }
+        double *o[kInfoArrays];
+        for (int i = 0; i < kInfoArrays; ++i)
+            o[i] = !ptr[i] ? nullptr : dev ? static_cast<double *>(ptr[i]) : d_scr[i]->p;
+        MP_HIP(hipMemcpyAsync(d_recs.p, recs.data(), sizeof(ScoreRec) * nr, hipMemcpyHostToDevice, stream));
+        MP_HIP(hipMemcpyAsync(d_jobs.p, jobs.data(), sizeof(InfoJob) * nr, hipMemcpyHostToDevice, stream));
+        if (!items.empty())
+            MP_HIP(hipMemcpyAsync(d_items.p, items.data(), sizeof(ResidItem) * items.size(), hipMemcpyHostToDevice,
+                                  stream));
+        if (timed) MP_HIP(hipEventRecord(t0.ev, stream));
+        MP_HIP(launch_information(stream, R.v, R.d_D.p, R.d_C.p, d_items.p, (int)items.size(), d_recs.p, d_jobs.p,
+                                  d_part.p));
+        if (timed) MP_HIP(hipEventRecord(t1.ev, stream));
+        MP_HIP(launch_information_finish(stream, R.v, d_jobs.p, (int)nr, d_part.p, o[0], o[1], o[2], o[3], d_out.p));
+        if (timed) MP_HIP(hipEventRecord(t2.ev, stream));
+        MP_HIP(hipMemcpyAsync(entries + r.e0, d_out.p, sizeof(InfoRecord) * nr, hipMemcpyDeviceToHost, stream));
+        for (int i = 0; i < kInfoArrays && !dev; ++i)
+            if (ptr[i])
+                MP_HIP(hipMemcpyAsync(static_cast<double *>(ptr[i]) + per[i] * (int64_t)r.e0, d_scr[i]->p,
+                                      sizeof(double) * (size_t)per[i] * nr, hipMemcpyDeviceToHost, stream));
+        MP_HIP(hipStreamSynchronize(stream)); // (records, items and the scratch are reused by the next run)
+        if (timed) {
+            float f = 0.f;
+            MP_HIP(hipEventElapsedTime(&f, t0.ev, t1.ev));
+            rows_ms += f;
+            MP_HIP(hipEventElapsedTime(&f, t1.ev, t2.ev));
+            finish_ms += f;
+        }
+        ++launches;
+    }
+    std::lock_guard<std::mutex> sl(g_info_mu);
+    g_info_launches += launches;
+    g_info_rows_ms += rows_ms;
+    g_info_finish_ms += finish_ms;
+}
+
 // ---- ransac's results into the caller's device arrays (mp_ransac_out_set) ----
 namespace {
 std::mutex g_rout_mu;

@@ -417,6 +417,38 @@ void residuals_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, c
 // their summed device milliseconds (events around each launch; measured only while profiling
 // is enabled).
 void residuals_stats(int64_t *launches, double *ms, bool reset);
+// The Gauss-Newton system of the estimators' cost over each model's inliers, and its inverse
+// (mp_information_set; kernels/information.h, host/information_plan.h,
+// include/mp_information.h).  Entries, pair_ids and factors as residuals_set.  Per entry e
+// (model m on pair p): m to problem units as residuals_set takes it; row i is a block of type t
+// iff bit t of residuals_set's mask is set for it (the same record, load_corr / eval_corr call
+// and thr_t * factor product); gating and job flags are make_lm_job(P, cfg, sizes, .., nonminimal
+// = false, m)'s (LO type, use_shift, the scale-only rule, w_sampson); the parameters are set up
+// as lm_setup.inc sets them up (bounds and feasibility are not read: nothing is optimised).
+// Row e of the outputs, all in problem units and in LmSystem's full 11-parameter layout:
+// out.H (66: packed upper triangle of J^T J), out.g (11: J^T r), out.cost (sum r^2 / 2),
+// out.cov (121: the inverse of H on the active set by info_covariance, zero elsewhere); each
+// nullable.  entries[e] (always host memory): the active mask, pd (1 inverted, 0 an active
+// H_aa or a pivot was not positive and finite: cov zero, -1 status 0: everything zero), status
+// (1: at least one block), rows = 2 (n0 + n1) + n2 after gating, counts = residuals_set's.
+// Every entry of g and H of an inactive parameter is exactly 0.0.  on_device / producer_stream
+// as ResidualsOut: device outputs are checked (memory of the set's device, aligned, inside
+// their allocations, pairwise disjoint) before any launch and written by the finishing kernel
+// directly.  A result depends on its entry alone.  Nothing of the set is written.
+// std::invalid_argument before the device is touched: residuals_set's cases (entries in place
+// of row_offsets and counts), and overlapping device outputs.
+struct InformationOut {
+    void *H = nullptr, *g = nullptr, *cost = nullptr, *cov = nullptr;
+    int32_t on_device = 0, pad = 0;
+    void *producer_stream = nullptr;
+};
+struct InfoRecord; // (host/information_plan.h; == mp_information_entry)
+void information_set(PairSet *set, int32_t num_entries, const int32_t *pair_ids, const Model *models,
+                     const double *factors, const InformationOut &out, InfoRecord *entries);
+// information_stats (mp_debug_information_stats): the runs since the last reset and the summed
+// device milliseconds of the two kernel stages (events; measured only while profiling is
+// enabled).
+void information_stats(int64_t *launches, double *rows_ms, double *finish_ms, bool reset);
 // ransac_adaptive_set (mp_ransac_adaptive_set): ransac_set's drawn mode with a per-pair
 // number of samples.  Samples go through draw -> hypothesize_run -> select_run in rounds of
 // `step` per still-active pair (checkpoints m_k = min(k step, budget)); select_run continues

@@ -4,6 +4,7 @@
 
 #include "../host/ingest_plan.h"
 #include "../host/pair_set_plan.h"
+#include "../host/information_plan.h"
 #include "../host/residuals_plan.h"
 #include "../include/mp_draw.h"
 #include "../include/mp_types.h"
@@ -183,6 +184,21 @@ hipError_t launch_inlier_mass(hipStream_t s, int variant, const PairData *Ds, co
 hipError_t launch_residuals(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
                             const ResidItem *items, int nitems, const ScoreRec *recs, unsigned char *mask,
                             double *errors, int64_t stride, ResidCount *out);
+
+// The Gauss-Newton system over a model's inliers and its inverse (information.h;
+// mp_information_set).  launch_information: one workgroup per item k (host/information_plan.h;
+// the items of launch_residuals), part[k] = the sums of the item's blocks under the record
+// recs[items[k].rec] and the job jobs[items[k].rec], and its three inlier counts.
+// launch_information_finish: one workgroup per entry j, the partials jobs[j].first_item ..
+// + nitems - 1 added in that order, masked and inverted; row jobs[j].out_row of H (66 doubles a
+// row), g (11), cost (1) and cov (121), each nullable and possibly memory of the caller, and
+// recs[j].  Nothing else is written.
+hipError_t launch_information(hipStream_t s, int variant, const PairData *Ds, const PairConst *Cs,
+                              const ResidItem *items, int nitems, const ScoreRec *recs, const InfoJob *jobs,
+                              InfoPartial *part);
+hipError_t launch_information_finish(hipStream_t s, int variant, const InfoJob *jobs, int nentries,
+                                     const InfoPartial *part, double *H, double *g, double *cost, double *cov,
+                                     InfoRecord *recs);
 
 // ransac's results into the caller's device arrays (ransac_out.h; mp_ransac_out_set).
 // launch_ransac_out: launch_residuals' items, rows and counts with the comparison err_t < thr_t

@@ -1828,6 +1828,8 @@ hipError_t launch_point_direct(hipStream_t s, int kind, const double *in, Model 
 #include "inlier_mass.h"
 // the errors and inlier mask of every correspondence under given models (mp_residuals_set)
 #include "residuals.h"
+// the Gauss-Newton system over a model's inliers and its inverse, per entry (mp_information_set)
+#include "information.h"
 // ransac's results into the caller's device arrays (mp_ransac_out_set)
 #include "ransac_out.h"
 // least-squares fits on random inlier subsets, many entries per launch (mp_lsq_fit_set)
